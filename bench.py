@@ -9,6 +9,14 @@ step's gather overlapping the next step's render) and rank 0 un-permutes them in
 (K3): strong scaling of a fixed frame.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload bench|head4096|batch10]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up the scenes, warms up, times the K steps, writes the last step's frames when
+--dump-outputs is given (DIR/scene<id>.npy, see dump_outputs) and prints the result line: value,
+ms_per_step and the kernel times the library records inside the timed region.  Everything else
+described below -- the per-sample counts and the roofline, end_to_end, moving_camera, the
+one-stream and per-scene legs, first_frame_ms, cpu_baseline, and at N > 1 the distributed report
+-- takes runs of its own and is made only with --full, which adds them to the same line.
 
 --workload (default "bench" = the BASELINE metric above) also runs BASELINE's other GPU
 configs: "head4096" = config 4 (head.dat, 4096x4096x16spp, the 8-GPU tile-shard case) and
@@ -823,6 +831,7 @@ def run_steps(work, world, rank, steps, warmup, dist=None, graph=False, clock_wa
         finish()                       # the last step's frames are assembled inside the timed region
     work.sync()
     work.span = (span0, span1)
+    work.last_set = (it[0] - 1) % nsets     # the buffer set the last step rendered into (dump_outputs)
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
@@ -875,6 +884,31 @@ def one_stream_steps(work, world, rank, dist, steps, warmup, kernel):
             "frame_latency_ms": round(lat, 4), "steps": steps, "warmup": warmup}
 
 
+DUMP_BUDGET = 64_000_000                # --dump-outputs: bytes of all the files together, at most
+
+
+def dump_outputs(work, world, out_dir):
+    """--dump-outputs (rank 0, right after the timed region): the frames the last timed step left in
+    device memory -- at N = 1 the buffer set that step rendered into, at N > 1 the frames rank 0
+    assembled from the gathered shards -- one file per scene, <out_dir>/scene<id>.npy.  A frame is
+    float32 [H, W, 3]: the B, G, R bytes of every BGRA8 pixel in memory order (the alpha byte is
+    always 0, as the reference's ToBGRA8 packs it).  Frames that together exceed DUMP_BUDGET
+    (head4096, batch10) are written as [n, 3]: the same n pixels of every frame, their row-major
+    indices drawn once from a fixed seed, ascending.  The scenes and cameras are the committed ones,
+    so two builds run with the same arguments write comparable files."""
+    os.makedirs(out_dir, exist_ok=True)
+    npix = W * H
+    per = (DUMP_BUDGET // len(SCENES) - 1024) // 12         # pixels per file: 3 float32 each + the header
+    idx = np.sort(np.random.default_rng(0).choice(npix, per, replace=False)) if per < npix else None
+    for i, (sid, hs, gs, f) in enumerate(work.scenes):
+        t = work.frames[i] if world > 1 else work.bufs[work.last_set][i]
+        px = t.cpu().numpy().view(np.uint32)
+        if idx is not None:
+            px = px[idx]
+        bgr = np.stack([(px >> s) & 255 for s in (0, 8, 16)], axis=-1).astype(np.float32)
+        np.save(os.path.join(out_dir, f"scene{sid}.npy"), bgr if idx is not None else bgr.reshape(H, W, 3))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -883,12 +917,20 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--kernel", type=int, default=0, help="rt_kernel value (0 = AUTO; see include/rt_tracer.h)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true")
-    ap.add_argument("--no-moving-camera", action="store_true")
-    ap.add_argument("--no-first-frame", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, everything else the benchmark measures: the per-sample counts "
+                         "and the roofline, the end-to-end and moving-camera legs, the one-stream and per-scene "
+                         "legs, the first frame, the CPU baseline and, at N > 1, the distributed report.  Without "
+                         "it a run sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the frames the last step rendered as DIR/scene<id>.npy "
+                         "(float32 B, G, R per pixel; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-end-to-end", action="store_true", help="with --full: skip the end-to-end leg")
+    ap.add_argument("--no-moving-camera", action="store_true", help="with --full: skip the moving-camera leg")
+    ap.add_argument("--no-first-frame", action="store_true", help="with --full: skip the first-frame leg")
     ap.add_argument("--no-legs", action="store_true",
-                    help="skip the one-stream and per-scene legs after the timed region")
+                    help="with --full: skip the one-stream and per-scene legs after the timed region")
     ap.add_argument("--overlap", choices=["on", "off"], default="on",
                     help="consecutive steps' batched launches on two streams with RT_KERNEL_FLAG_OVERLAP (one "
                          "step's tail under the next step's start); off: one stream")
@@ -944,9 +986,11 @@ def main():
     # other GPU work: profiles/r04t_frame_series_cold.json, r04final_series_burn.json).  The K timed
     # steps are the same launches either way.  (first_frame makes fresh scenes -- host setup, an idle
     # GPU -- so it runs after the timed region.)
-    ab = {sid: algorithmic_bytes(gs, f) for sid, hs, gs, f in work.scenes} if rank == 0 else None
+    # All of these take runs of their own, so only --full makes them; a plain run goes straight to
+    # run_steps, whose clock warm-up renders stand in for the sustained GPU work.
+    ab = {sid: algorithmic_bytes(gs, f) for sid, hs, gs, f in work.scenes} if rank == 0 and args.full else None
     extra = {}
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         if args.workload == "bench" and not args.no_end_to_end:
             extra["end_to_end"] = end_to_end(rtm, work)
         if not args.graph and not args.no_moving_camera:
@@ -957,12 +1001,14 @@ def main():
     kernel_ms = work.kernel_ms(args.steps)
     latency = dict(work.latency)
     step_ms = work.span_ms(args.steps)
-    drep = dist_report(work, world, rank, dist, args.steps, elapsed) if world > 1 else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(work, world, args.dump_outputs)    # before any leg renders into the buffers again
+    drep = dist_report(work, world, rank, dist, args.steps, elapsed) if world > 1 and args.full else None
     # the supplementary legs after the timed region (the bench value above is final): the step with one
-    # stream (no overlap), and each bench scene alone; bounded so the default run stays short
+    # stream (no overlap), and each bench scene alone; bounded so the --full run stays short
     leg_steps, leg_warm = min(args.steps, 50), min(args.warmup, 10)
     legs = {}
-    if args.workload == "bench" and not args.no_legs:
+    if args.full and args.workload == "bench" and not args.no_legs:
         if work.overlap:
             legs["one_stream"] = one_stream_steps(work, world, rank, dist if world > 1 else None, leg_steps,
                                                   leg_warm, args.kernel)
@@ -972,19 +1018,23 @@ def main():
     value = samples_per_step * args.steps / elapsed / 1e6
 
     if rank == 0:
-        # algorithmic bytes per launch (this rank's launch covers 1/world of the frame)
-        launch_bytes = {sid: ab[sid]["bytes_per_sample"] * W * H * SPP / world for sid in SCENES}
-        achieved = sum(launch_bytes.values()) / (step_ms / 1e3)
-        roof = valu_roofline(rtm, kernel_ms, args, world, achieved, step_ms, work,
-                             scene_ms=legs.get("per_scene_steps"))
-        roof["duration"] = {"ms_per_step": round(step_ms, 4), "launches": args.steps * work.launches_per_step(),
-                            "source": "HIP events on the launch stream around all the timed steps' render launches "
-                                      "(gaps and the every-16th-frame plan kernel included: a conservative duration)"}
+        roof = None
+        if ab is not None:
+            # algorithmic bytes per launch (this rank's launch covers 1/world of the frame)
+            launch_bytes = {sid: ab[sid]["bytes_per_sample"] * W * H * SPP / world for sid in SCENES}
+            achieved = sum(launch_bytes.values()) / (step_ms / 1e3)
+            roof = valu_roofline(rtm, kernel_ms, args, world, achieved, step_ms, work,
+                                 scene_ms=legs.get("per_scene_steps"))
+            roof["duration"] = {"ms_per_step": round(step_ms, 4), "launches": args.steps * work.launches_per_step(),
+                                "source": "HIP events on the launch stream around all the timed steps' render launches "
+                                          "(gaps and the every-16th-frame plan kernel included: a conservative duration)"}
         per_scene = {}
         for sid in SCENES:
-            e = {"bytes_per_sample": round(ab[sid]["bytes_per_sample"], 1), "survey_bytes_per_sample": SURVEY_B[sid],
-                 "voxels": round(ab[sid]["voxels"], 2), "tri_tests": round(ab[sid]["tri_tests"], 2),
-                 "hit": round(ab[sid]["hit"], 4)}
+            e = {}
+            if ab is not None:
+                e = {"bytes_per_sample": round(ab[sid]["bytes_per_sample"], 1), "survey_bytes_per_sample": SURVEY_B[sid],
+                     "voxels": round(ab[sid]["voxels"], 2), "tri_tests": round(ab[sid]["tri_tests"], 2),
+                     "hit": round(ab[sid]["hit"], 4)}
             if sid in kernel_ms:
                 e.update({"kernel_ms": round(kernel_ms[sid], 4), "kernel_ms_samples": work.samples.get(sid),
                           "kernel_msamples_per_s": round(W * H * SPP / world / kernel_ms[sid] / 1e3, 1)})
@@ -994,6 +1044,7 @@ def main():
             "value": round(value, 3),
             "unit": "Msamples/s",
             "n_gpus": world,
+            "full": args.full,
             "steps": args.steps,
             "warmup": args.warmup,
             "clock_warmup": getattr(work, "clock_warmup", None),
@@ -1048,9 +1099,9 @@ def main():
             mc = extra["moving_camera"]
             mc["vs_static"] = round(elapsed / args.steps * 1e3 / mc["ms_per_step"], 4)
             out["moving_camera"] = mc
-        if world == 1 and args.workload == "bench" and not args.no_first_frame:
+        if args.full and world == 1 and args.workload == "bench" and not args.no_first_frame:
             out["first_frame_ms"] = first_frame(rtm, torch)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
 

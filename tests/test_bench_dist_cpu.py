@@ -137,7 +137,7 @@ def test_bench_two_ranks_one_gpu_rehearsal():
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--check", "--dist-backend", "gloo",
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--check", "--dist-backend", "gloo",
            "--one-device"]
     r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=220)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -35,16 +35,16 @@ if [ "$PART" = A ]; then
     exit 0
 fi
 if [ "$PART" = B ]; then
-    run bench 300 python -u bench.py
-    run bench_head4096 300 python -u bench.py --workload head4096 --no-end-to-end --no-moving-camera
-    run bench_batch10 300 python -u bench.py --workload batch10 --no-end-to-end --no-moving-camera
-    run bench_s20w5 150 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline
+    run bench 300 python -u bench.py --full
+    run bench_head4096 300 python -u bench.py --full --workload head4096 --no-end-to-end --no-moving-camera
+    run bench_batch10 300 python -u bench.py --full --workload batch10 --no-end-to-end --no-moving-camera
+    run bench_s20w5 150 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
     run series_burn 100 python3 -u tools/frame_series.py --steps 60 --burn 1500 --out ${T}_series_burn
     exit 0
 fi
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/${T}_trace -o run -- \
-    python3 $R/bench.py --no-cpu-baseline --no-end-to-end --no-moving-camera --no-first-frame \
+    python3 $R/bench.py --full --no-cpu-baseline --no-end-to-end --no-moving-camera --no-first-frame \
     > $R/gpurun_out/${T}_bench_under_rocprof.json 2> $R/gpurun_out/${T}_trace.err
 rc=$?; echo "trace rc=$rc"; [ $rc -eq 0 ] || exit $rc
 cd $R
