@@ -63,7 +63,7 @@ TRACER_SYMBOLS = [
     "rt_sample_table", "rt_last_error", "rt_abi_version", "rt_grid_build", "rt_grid_free",
     "rt_scene_create_from_mesh", "rt_kernel_times", "rt_render_frame_host", "rt_frame_host_wait", "rt_host_alloc",
     "rt_host_free", "rt_render_hits_device", "rt_scene_info_get", "rt_build_hash", "rt_render_batch_device",
-    "rt_render_records_device", "rt_render_frame_host_tiled",
+    "rt_render_records_device", "rt_render_frame_host_tiled", "rt_fref_buffer_bytes",
 ]
 MAX_BATCH = 10                           # frames per rt_render_batch_device launch (kMaxBatch)
 
@@ -184,6 +184,8 @@ def tracer_lib():
         if hasattr(L, "rt_render_records_device"):   # ABI 8
             L.rt_render_records_device.argtypes = [vp, ctypes.POINTER(Frame), c_u32, c_u32, c_u32, vp,
                                                    ctypes.POINTER(Tile), vp, vp]
+        if hasattr(L, "rt_fref_buffer_bytes"):       # absent in earlier builds (A/B runs)
+            L.rt_fref_buffer_bytes.argtypes = [c_u32, ctypes.POINTER(ctypes.c_uint64)]
         L.rt_unshard_device.argtypes = [c_u32, c_u32, c_u32, vp, vp, vp]
         L.rt_last_kernel_ms.argtypes = [vp, ctypes.POINTER(c_f32)]
         L.rt_trace_samples.argtypes = [vp, ctypes.POINTER(Frame), c_u32, c_u32, c_u32, c_u32, vp]
@@ -281,6 +283,14 @@ def library_build_hash():
     buf = ctypes.create_string_buffer(64)
     _check(L.rt_build_hash(buf, 64), L, "rt_build_hash")
     return buf.value.decode()
+
+
+def fref_buffer_bytes(nrefs):
+    """Bytes of one of a scene's two per-camera-origin record buffers (rt_fref_buffer_bytes): the
+    records plus the zero pad the wave-uniform record loop may load.  Needs no GPU."""
+    L, b = tracer_lib(), ctypes.c_uint64(0)
+    _check(L.rt_fref_buffer_bytes(int(nrefs), ctypes.byref(b)), L, "rt_fref_buffer_bytes")
+    return b.value
 
 
 def device_count():

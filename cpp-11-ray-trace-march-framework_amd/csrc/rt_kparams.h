@@ -15,6 +15,13 @@ constexpr uint32_t kTile = 16;              // shard / scheduling tile edge (pix
 constexpr uint32_t kTilePix = kTile * kTile;
 constexpr uint32_t kWG = 256;               // lanes per workgroup
 constexpr uint32_t kWavesPerWG = kWG / 64u;
+// Zero records past the last one of each per-origin record buffer (KParams::frefs): the wave-uniform
+// record loop loads its next record without a range test, up to one record (2 x kWavesPerWG covers a
+// strided loop over two register sets) past a cell list's end.  k_origin_pre writes only the scene's
+// records, so the pad stays zero; a zero record has det = 0 and could never be accepted.
+constexpr uint32_t kFrefPad = 2u * kWavesPerWG;
+// bytes of one per-origin record buffer of a scene with nrefs CSR references (64-byte records)
+constexpr size_t fref_buffer_bytes(uint32_t nrefs) { return (size_t(nrefs ? nrefs : 1u) + kFrefPad) * 64u; }
 // Traversal features, combined into the VAR template argument of the render kernels.
 constexpr int kVarWaveGate = 2;             // skip a test's second half when no lane needs it
 constexpr int kVarSkipRun = 4;              // wave-uniform proven-empty runs in a tight loop

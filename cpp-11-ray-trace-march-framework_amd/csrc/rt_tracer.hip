@@ -12,8 +12,9 @@
 //   cell_off  u32[C+1]            CSR offsets (scenes whose lists do not fit the packed word)
 //   refs      float4[3*R]         one 48-B record per CSR reference, in CSR order:
 //                                 {v0.xyz, e1.x} {e1.yz, e2.xy} {e2.z, tri_idx bits, 0, 0}
-//   frefs     float4[4*R]         per camera origin (k_origin_pre), one 64-B record per CSR
-//                                 reference: the origin-only terms of triangle.h:82-98
+//   frefs     float4[4*(R+pad)]   per camera origin (k_origin_pre), one 64-B record per CSR
+//                                 reference: the origin-only terms of triangle.h:82-98; then
+//                                 kFrefPad zero records (the uniform record loop's look-ahead)
 //   shade     float4[3*T]         per triangle the 3 vertex normals (shading of a hit)
 //   face_n    float4[T]           face normal (IntersectRayTriBarycentric only)
 
@@ -1256,11 +1257,16 @@ int rt_scene_create(const rt_scene_desc *d, int device, rt_scene **out)
     for (uint32_t c = 0; c < nc; c++)
         s->max_cell_refs = std::max(s->max_cell_refs, g.cell_offsets[c + 1] - g.cell_offsets[c]);
 
-    const size_t nfrefs = size_t(std::max(nr, 1u)) * 4;
+    // the per-origin record buffers end in kFrefPad zero records (rt_kparams.h): zeroed once here,
+    // k_origin_pre writes only the nr records in front of them (the blocking copies below follow the
+    // memsets on the null stream, so the pad is zero before any launch can read it)
+    const size_t nfrefs = rtk::fref_buffer_bytes(nr) / sizeof(float4);
     RT_HIP(hipMalloc(&s->d_off, sizeof(uint32_t) * (nc + 1)));
     RT_HIP(hipMalloc(&s->d_refs, sizeof(float4) * refs.size()));
     RT_HIP(hipMalloc(&s->d_frefs[0], sizeof(float4) * nfrefs));
     RT_HIP(hipMalloc(&s->d_frefs[1], sizeof(float4) * nfrefs));
+    RT_HIP(hipMemset(s->d_frefs[0], 0, sizeof(float4) * nfrefs));
+    RT_HIP(hipMemset(s->d_frefs[1], 0, sizeof(float4) * nfrefs));
     RT_HIP(hipMalloc(&s->d_shade, sizeof(float4) * shade.size()));
     RT_HIP(hipMalloc(&s->d_facen, sizeof(float4) * facen.size()));
     RT_HIP(hipMemcpy(s->d_off, g.cell_offsets, sizeof(uint32_t) * (nc + 1), hipMemcpyHostToDevice));
@@ -1440,6 +1446,13 @@ int rt_scene_destroy(rt_scene *s)
 
     }
     delete s;
+    return RT_OK;
+}
+
+int rt_fref_buffer_bytes(uint32_t nrefs, uint64_t *bytes)
+{
+    if (!bytes) return fail(RT_E_INVALID, "NULL argument");
+    *bytes = rtk::fref_buffer_bytes(nrefs);
     return RT_OK;
 }
 

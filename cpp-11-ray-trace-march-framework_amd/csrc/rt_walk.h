@@ -154,6 +154,7 @@ typedef float vf4 __attribute__((ext_vector_type(4)));
 // constant address space: uniform loads of memory no store of the render kernels touches (frefs
 // are written by k_origin_pre, an earlier launch) select s_load through the scalar cache
 typedef const __attribute__((address_space(4))) vf4 cvf4;
+typedef float vf16 __attribute__((ext_vector_type(16)));    // one 64-byte record in 16 SGPRs
 
 // The per-lane list loop of the per-camera-record test: this lane's list [kb, ke) in order
 // (grid.cpp:243-267), lowering tb on every accepted hit.  The first-half terms (r0..r2) per
@@ -252,7 +253,15 @@ __device__ __forceinline__ bool test_cell(const KParams& P, float ox, float oy, 
                 // software pipeline over two register sets in turn: record k + 1 is in flight
                 // while record k is tested, with no per-record register copies (scalar loads may
                 // return out of order, so each set is waited for where it is first read)
-                auto test_rec = [&](const vf4 r0, const vf4 r1, const vf4 r2, const vf4 r3, uint32_t k) {
+                //
+                // rec_k: list position of the record `ahead` records past p (formed where a hit is
+                // taken: the empty asm keeps it from becoming a second loop counter)
+                auto rec_k = [&](cvf4 *p, uint32_t ahead) {
+                    uint64_t d = uint64_t(p) - uint64_t(crefs);
+                    asm("" : "+s"(d));
+                    return uint32_t(d >> 6) + ahead;
+                };
+                auto test_rec = [&](const vf4 r0, const vf4 r1, const vf4 r2, const vf4 r3, auto pos) {
                     if (STATS) tests++;
                     // the gate skips the record's second half AND the acceptance for the whole
                     // wave when no lane passes det and u (the common case in a dense cell)
@@ -269,10 +278,52 @@ __device__ __forceinline__ bool test_cell(const KParams& P, float ox, float oy, 
                         tb = take ? ct : tb;
                         u = take ? cu : u;
                         v = take ? cv : v;
+                        const uint32_t k = pos();          // wave-uniform, outside the select
                         tri = take ? k : tri;
                     }
                 };
                 cvf4 *np = crefs + size_t(kfirst) * 4u;
+                if constexpr (!SPLIT)
+                {
+                    // A running record pointer over PAIRS of records, then the odd one: the loop has
+                    // one exit, so its test is one scalar compare and branch per two records (a
+                    // second exit in the middle makes the compiler carry the exit condition as a
+                    // lane mask).  The next record is ALWAYS loaded: the buffers end in kFrefPad
+                    // zero records (rt_kparams.h), so the load one record past the list's end is in
+                    // bounds, and what it returns is never tested.  The list position is formed
+                    // only where a hit is taken (rec_k).  The loads and their waits are asm
+                    // statements, which keep their order: written as plain loads, the compiler
+                    // sinks each load to its first use and the pipeline is gone.  Each wait names
+                    // the set it is for, so that set is read after it and stays allocated until its
+                    // load has returned (the last load's data is dropped).
+                    const uint32_t n = ke0 - kb0;
+                    cvf4 *const endp = np + size_t(n >> 1) * 8u;
+                    vf16 a, b;
+                    asm volatile("s_load_dwordx16 %0, %1, 0x0" : "=&s"(a) : "s"(np));
+                    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a));
+                    if (np != endp)
+                        do
+                        {
+                            asm volatile("s_load_dwordx16 %0, %1, 0x40" : "=&s"(b) : "s"(np));
+                            test_rec(vf4{a[0], a[1], a[2], a[3]}, vf4{a[4], a[5], a[6], a[7]},
+                                     vf4{a[8], a[9], a[10], a[11]}, vf4{a[12], a[13], a[14], a[15]},
+                                     [&] { return rec_k(np, 0u); });
+                            asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(b));
+                            asm volatile("s_load_dwordx16 %0, %1, 0x80" : "=&s"(a) : "s"(np));
+                            test_rec(vf4{b[0], b[1], b[2], b[3]}, vf4{b[4], b[5], b[6], b[7]},
+                                     vf4{b[8], b[9], b[10], b[11]}, vf4{b[12], b[13], b[14], b[15]},
+                                     [&] { return rec_k(np, 1u); });
+                            asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a));
+                            np += 8;
+                            asm volatile("" : "+s"(np));    // the pointer itself is the loop counter
+                        } while (np != endp);
+                    if (n & 1u)
+                        test_rec(vf4{a[0], a[1], a[2], a[3]}, vf4{a[4], a[5], a[6], a[7]},
+                                 vf4{a[8], a[9], a[10], a[11]}, vf4{a[12], a[13], a[14], a[15]},
+                                 [&] { return rec_k(np, 0u); });
+                }
+                else
+                {
                 vf4 a0 = np[0], a1 = np[1], a2 = np[2], a3 = np[3];
                 for (uint32_t k = kfirst;; k += 2u * kstep)
                 {
@@ -286,7 +337,7 @@ __device__ __forceinline__ bool test_cell(const KParams& P, float ox, float oy, 
                         b2 = np[2];
                         b3 = np[3];
                     }
-                    test_rec(a0, a1, a2, a3, k);
+                    test_rec(a0, a1, a2, a3, [&] { return k; });
                     if (!more1) break;
                     const bool more2 = k + 2u * kstep < ke0;
                     if (more2)
@@ -297,8 +348,9 @@ __device__ __forceinline__ bool test_cell(const KParams& P, float ox, float oy, 
                         a2 = np[2];
                         a3 = np[3];
                     }
-                    test_rec(b0, b1, b2, b3, k + kstep);
+                    test_rec(b0, b1, b2, b3, [&] { return k + kstep; });
                     if (!more2) break;
+                }
                 }
             }
             uniform_done = true;

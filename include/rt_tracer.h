@@ -170,6 +170,10 @@ int  rt_scene_create(const rt_scene_desc *desc, int device, rt_scene **out);
 int  rt_scene_destroy(rt_scene *scene);
 /* device bytes held by the scene (all arrays) */
 int  rt_scene_device_bytes(const rt_scene *scene, uint64_t *bytes);
+/* bytes of ONE of a scene's two per-camera-origin record buffers for `nrefs` cell references: 64 bytes
+ * per reference (at least one) plus the zero pad records the wave-uniform record loop may load past a
+ * cell list's end.  rt_scene_device_bytes counts two of them.  Needs no GPU. */
+int  rt_fref_buffer_bytes(uint32_t nrefs, uint64_t *bytes);
 
 /* ---- grid build on the GPU (Grid::Grid, grid.cpp:12-154; grid.h:15) ----------------------
  * Voxelizes the mesh into the reference's uniform grid on `device`: the same AABB, cell size
