@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/rt_tracer.h"
+#include "rt_fref_slots.h"
 #include "rt_internal.h"
 #include "rt_kparams.h"
 
@@ -101,12 +102,10 @@ struct rt_scene
     // Per-camera-origin records (k_origin_pre), TWO buffers: a frame whose origin is in neither computes
     // its records into the one the scene's last launch does not read, so consecutive frames of a moving
     // camera may still overlap (RT_KERNEL_FLAG_OVERLAP): the launch before the last -- the only other one
-    // in flight -- is waited for first (order_overlap).  fref_org: each buffer's origin (bit patterns),
-    // fref_ok: computed; fref_last: bit b = the last launch reads buffer b.
+    // in flight -- is waited for first (order_overlap).  fref: what each buffer holds and which ones the
+    // last launch reads (rt_fref_slots.h, whose functions choose the buffer).
     float4 *d_frefs[2] = { nullptr, nullptr };
-    bool fref_ok[2] = { false, false };
-    uint32_t fref_org[2][3] = { { 0, 0, 0 }, { 0, 0, 0 } };
-    uint32_t fref_last = 0;
+    rtk::FrefSlots fref;
     uint64_t *d_clk = nullptr;      // RT_KERNEL_FLAG_WAVE_CLOCK records of the last such launch
     size_t clk_cap = 0;
     uint32_t clk_items = 0;

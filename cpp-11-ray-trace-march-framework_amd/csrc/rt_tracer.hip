@@ -171,6 +171,7 @@ int wait_scene_idle(rt_scene *s)
     if (s->ev_recorded) RT_HIP(hipEventSynchronize(s->ev_last->ev));
     if (s->ev_prev) RT_HIP(hipEventSynchronize(s->ev_prev->ev));
     s->ev_prev.reset();
+    rtk::fref_ordered(s->fref);                 // nothing still reads a per-origin record buffer
     return RT_OK;
 }
 
@@ -186,8 +187,12 @@ hipError_t wait_unless_done(hipStream_t st, hipEvent_t e)
 // predecessor (ev_prev).  The caller's next launch on st then follows them all.
 // The last launch becomes the "launch two back" of the next one: an overlapped launch after this one
 // on a third stream is ordered by nothing else.
+// No earlier launch then still reads a per-origin record buffer when the caller's launch starts, so that
+// launch may recompute either one (fref_ordered); a launch after it that asks to overlap it waits for
+// this one's predecessors too (ev_prev above), whatever becomes of the caller's launch.
 int order_all(rt_scene *s, hipStream_t st)
 {
+    rtk::fref_ordered(s->fref);
     if (!s->ev_recorded) return RT_OK;
     if (st != s->last_stream) RT_HIP(wait_unless_done(st, s->ev_last->ev));
     if (s->ev_prev && s->prev_stream != st) RT_HIP(wait_unless_done(st, s->ev_prev->ev));
@@ -441,45 +446,27 @@ uint32_t env_tunable(const char *name, uint32_t dflt)
     return e && *e ? uint32_t(std::strtoul(e, nullptr, 0)) : dflt;
 }
 
-// The per-origin record buffer a frame of origin `org` reads (rt_scene::d_frefs): the one holding that
-// origin, else the one to compute it into -- never one the scene's last launch reads (mask `busy`, bit b:
-// buffer b), preferring an empty one.  -1: both are busy (a batch that read two origins of the scene).
-int fref_slot(const rt_scene *s, const float org[3], uint32_t busy, bool *compute)
-{
-    uint32_t ob[3];
-    std::memcpy(ob, org, sizeof(ob));
-    for (int b = 0; b < 2; b++)
-        if (s->fref_ok[b] && std::memcmp(ob, s->fref_org[b], sizeof(ob)) == 0)
-        {
-            *compute = false;
-            return b;
-        }
-    *compute = true;
-    for (int b = 0; b < 2; b++)
-        if (!(busy & (1u << b)) && !s->fref_ok[b]) return b;
-    for (int b = 0; b < 2; b++)
-        if (!(busy & (1u << b))) return b;
-    return -1;
-}
-
 // A frame of this origin may overlap the scene's last launch (RT_KERNEL_FLAG_OVERLAP) as far as the
-// per-origin records go: its origin is computed, or the buffer it would be computed into is one the last
-// launch does not read.
+// per-origin records go (rt_fref_slots.h).
 bool fref_overlap_ok(const rt_scene *s, const float org[3])
 {
-    bool compute;
-    return fref_slot(s, org, s->fref_last, &compute) >= 0;
+    uint32_t ob[3];
+    rtk::fref_bits(org, ob);
+    return rtk::fref_overlap_ok(s->fref, ob);
 }
 
-// The per-reference origin terms for this frame's camera origin in a buffer of their own (fref_slot),
-// computed when neither buffer holds them (a moving camera pays one small launch per frame), ordered after
-// every launch that may still read that buffer (the caller has ordered st after the launch before the
-// last one, which is the only other one in flight; busy: buffers that launches of this call read already).
+// The per-reference origin terms for this frame's camera origin in a buffer of their own
+// (rtk::fref_slot_for_launch), computed when neither buffer holds them (a moving camera pays one small
+// launch per frame), ordered after every launch that may still read that buffer: the caller has ordered
+// st after the launch before the last one and -- unless this launch overlaps it, when its buffers count as
+// busy -- after the last one (order_all); busy: buffers that frames of this call read already.
 // Sets P.frefs and marks the buffer in *used.
 int ensure_origin_terms(rt_scene *s, KParams& P, hipStream_t st, uint32_t busy, uint32_t *used)
 {
     bool compute = false;
-    const int b = fref_slot(s, P.org, s->fref_last | busy, &compute);
+    uint32_t ob[3];
+    rtk::fref_bits(P.org, ob);
+    const int b = rtk::fref_slot_for_launch(s->fref, ob, busy, &compute);
     if (b < 0) return fail(RT_E_INVALID, "internal: no free per-origin record buffer");
     if (compute)
     {
@@ -487,8 +474,7 @@ int ensure_origin_terms(rt_scene *s, KParams& P, hipStream_t st, uint32_t busy, 
             hipLaunchKernelGGL(origin_pre_kernel(), dim3((s->nrefs + kWG - 1) / kWG), dim3(kWG), 0, st, s->d_refs,
                                s->d_frefs[b], s->nrefs, P.org[0], P.org[1], P.org[2]);
         RT_HIP(hipGetLastError());
-        std::memcpy(s->fref_org[b], P.org, sizeof(s->fref_org[b]));
-        s->fref_ok[b] = true;
+        rtk::fref_computed(s->fref, b, ob);
     }
     P.frefs = s->d_frefs[b];
     *used |= 1u << b;
@@ -563,17 +549,17 @@ int launch_render(rt_scene *s, const rt_frame *f, KParams& P, uint32_t n_local_t
               ((f->kernel & RT_KERNEL_FLAG_WAVE_CLOCK) ? kVarWaveClock : 0);
         uint32_t used = 0;
         if (int rc = ensure_origin_terms(s, P, st, 0u, &used)) return rc;
-        s->fref_last = used;
+        rtk::fref_launched(s->fref, used);
         g_ht.mark("origin");
     }
     else
-        s->fref_last = 0u;                      // (this launch reads no per-origin records)
-    if (auto_path)
-        ;
-    else if (lanes && P.isect == RT_ISECT_RAY_MARCH)
-        var = kVarMarch | ((f->kernel & RT_KERNEL_FLAG_EXHAUSTIVE) ? kVarExhaustive : 0);
-    else if (lanes && P.isect == RT_ISECT_BRUTE_FORCE)
-        var = kVarBrute;
+    {
+        rtk::fref_launched(s->fref, 0u);        // (this launch reads no per-origin records)
+        if (lanes && P.isect == RT_ISECT_RAY_MARCH)
+            var = kVarMarch | ((f->kernel & RT_KERNEL_FLAG_EXHAUSTIVE) ? kVarExhaustive : 0);
+        else if (lanes && P.isect == RT_ISECT_BRUTE_FORCE)
+            var = kVarBrute;
+    }
     // kernel-time events only outside stream capture (a captured record has no time to read)
     // A timed event pair costs ~10 us of device time per launch (measured: bench step 0.755 ->
     // 0.736 ms without), so only every time_every-th launch is timed (rt_scene_set_timing)
@@ -792,6 +778,25 @@ int launch_batch(rt_scene *const *S, const rt_frame *F, uint32_t n, KParams *P, 
     const uint64_t fblocks = uint64_t(n_local_tiles) * wgpt;
     const uint64_t blocks = fblocks * n;
     if (blocks > 0x3FFFFFFFull) return RT_E_INVALID;        // one launch per frame (each checks its own size)
+    // A scene has two per-origin record buffers, all of them this launch's to read: frames of one scene at
+    // more than two DISTINCT camera origins cannot share a launch.  norg[i]: the distinct origins of frame
+    // i's scene among frames 0 .. i.
+    uint32_t norg[kMaxBatch] = {};
+    for (uint32_t i = 0; i < n; i++)
+    {
+        uint32_t seen[2][3], ob[3], nseen = 0;
+        for (uint32_t j = 0; j <= i; j++)
+        {
+            if (S[j] != S[i]) continue;
+            rtk::fref_bits(P[j].org, ob);
+            bool fresh = true;
+            for (uint32_t k = 0; k < nseen; k++) fresh = fresh && std::memcmp(ob, seen[k], sizeof(ob)) != 0;
+            if (!fresh) continue;
+            if (nseen == 2u) return RT_E_INVALID;           // a third origin: one launch per frame
+            std::memcpy(seen[nseen++], ob, sizeof(ob));
+        }
+        norg[i] = nseen;
+    }
     *batched = true;
     KBatch KB;
     std::memset(&KB, 0, sizeof(KB));
@@ -824,18 +829,9 @@ int launch_batch(rt_scene *const *S, const rt_frame *F, uint32_t n, KParams *P, 
     for (uint32_t i = 0; i < n; i++)
     {
         overlap = overlap && (F[i].kernel & RT_KERNEL_FLAG_OVERLAP) && !S[i]->tab_dirty && fref_overlap_ok(S[i], P[i].org);
-        // a scene twice in the batch at another origin: both record buffers are this launch's, so it
-        // orders after every launch of the scene; more than two origins of one scene: no batch
-        uint32_t org_i[3], org_j[3];
-        std::memcpy(org_i, P[i].org, sizeof(org_i));
-        int others = 0;
-        for (uint32_t j = 0; j < i; j++)
-        {
-            std::memcpy(org_j, P[j].org, sizeof(org_j));
-            if (S[j] == S[i] && std::memcmp(org_i, org_j, sizeof(org_i)) != 0) others++;
-        }
-        if (others) overlap = false;
-        if (others > 1) return RT_E_INVALID;
+        // a scene in the batch at two origins: both record buffers are this launch's, so it orders after
+        // every launch of the scene
+        if (norg[i] > 1u) overlap = false;
     }
     if (overlap && (front || wide_heavy))
     {
@@ -873,7 +869,7 @@ int launch_batch(rt_scene *const *S, const rt_frame *F, uint32_t n, KParams *P, 
     {
         bool first = true;
         for (uint32_t j = 0; j < i; j++) first = first && S[j] != S[i];
-        if (first) S[i]->fref_last = used[i];
+        if (first) rtk::fref_launched(S[i]->fref, used[i]);
     }
     if (front || wide_heavy)
         if (int rc = hf_prepare(s0, P[0], blocks, kvar, front, st, ident | 1u, cams)) return rc;
@@ -1888,6 +1884,7 @@ int rt_render_frame_host_tiled(rt_scene *s, const rt_frame *f, uint32_t *h_tiles
         if (s->ev_prev) RT_HIP(hipStreamWaitEvent(st[0], s->ev_prev->ev, 0));
         s->ev_prev.reset();
     }
+    rtk::fref_ordered(s->fref);                 // (so either per-origin record buffer may be recomputed)
     KParams P0;
     frame_params(s, f, P0);
     if (use_lanes(f, spp) && P0.isect == RT_ISECT_GRID && P0.tri_test == RT_TRI_MOLLER_TRUMBORE &&
@@ -1895,7 +1892,7 @@ int rt_render_frame_host_tiled(rt_scene *s, const rt_frame *f, uint32_t *h_tiles
     {
         uint32_t used = 0;                      // (every launch before this one is waited for above)
         if ((rc = ensure_origin_terms(s, P0, st[0], 0u, &used))) return rc;
-        s->fref_last = used;
+        rtk::fref_launched(s->fref, used);
     }
     if ((rc = flush_tables(s, st[0]))) return rc;      // before the fork: both streams read them
     RT_HIP(hipEventRecord(s->ev_t_fork, st[0]));

@@ -1,0 +1,254 @@
+// fref_slot_check.cpp -- exhaustive model check of the per-origin record buffer policy
+// (csrc/rt_fref_slots.h), the functions librt_tracer.so itself runs.
+//
+//   fref_slot_check [depth = 4] [origins = 4]
+//
+// Every sequence of `depth` launches on one scene over `origins` camera origins.  Launch kinds: a single
+// frame; a batch of 2 frames (1 or 2 distinct origins); a batch of 3 frames with a repeat (X, X, Y and its
+// permutations) -- each ordered after every earlier launch, or asking to overlap the last one, which the
+// library grants only to a launch of one distinct origin that fref_overlap_ok accepts (launch_batch,
+// launch_render; an overlap refused for any other reason is an ordered launch).
+//
+// launch() below drives the header exactly as rt_tracer.hip does (order_all -> fref_ordered;
+// ensure_origin_terms -> fref_slot_for_launch + fref_computed; fref_launched).  Everything it is checked
+// against is kept here, without the header's masks: what each buffer truly holds, which launches may still
+// run and what they read.
+//
+// Prints one JSON object; exit status 0 also with violations (the test reads the counts).
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../cpp-11-ray-trace-march-framework_amd/csrc/rt_fref_slots.h"
+
+namespace {
+
+struct Kind { int n; int org[3]; bool ask; int distinct; uint32_t ob[3][3]; };
+
+enum { V_NO_SLOT, V_OVERLAP_NO_SLOT, V_RUNNING, V_SAME_LAUNCH, V_ORIGIN_AT_ISSUE, V_ORIGIN_AT_END, V_MISSING_WAIT, V_KINDS };
+const char *const kNames[V_KINDS] = { "ordered_launch_without_slot", "overlapped_launch_without_slot",
+                                      "recompute_of_running_launchs_buffer", "recompute_of_same_launchs_buffer",
+                                      "wrong_origin_at_issue", "wrong_origin_at_end", "overlap_needs_missing_wait" };
+
+// the checker's own picture of the scene
+struct Truth
+{
+    int holds[2];           // origin whose records buffer b holds (the last k_origin_pre into it), -1: none
+    uint32_t last_reads;    // buffers the last launch reads
+    uint32_t prev_reads;    // buffers the launch before it reads, while that one may still run (else 0)
+    bool any;               // a launch was issued
+};
+
+struct State { rtk::FrefSlots f; Truth t; };
+
+struct Tally
+{
+    uint64_t sequences = 0, launches = 0, overlaps = 0, recomputes = 0, v[V_KINDS] = {};
+    int short_len = 0;      // the shortest violating sequence seen (0: none)
+    std::string short_seq;
+};
+
+Kind make_kind(int n, int a, int b, int c, bool ask)
+{
+    Kind k = { n, { a, b, c }, ask, 0, {} };
+    for (int i = 0; i < n; i++)
+    {
+        const float o[3] = { float(k.org[i]) + 0.5f, -1.0f, 0.25f * float(k.org[i]) };
+        rtk::fref_bits(o, k.ob[i]);
+        bool fresh = true;
+        for (int j = 0; j < i; j++) fresh = fresh && k.org[j] != k.org[i];
+        k.distinct += fresh;
+    }
+    return k;
+}
+
+std::string show(const Kind *const *seq, int len)
+{
+    std::string s;
+    for (int i = 0; i < len; i++)
+    {
+        s += i ? " " : "";
+        s += seq[i]->ask ? "overlap[" : "ordered[";
+        for (int k = 0; k < seq[i]->n; k++) s += std::string(k ? "," : "") + char('A' + seq[i]->org[k]);
+        s += "]";
+    }
+    return s;
+}
+
+// One launch; false: the library returns an error (no slot), the sequence ends there.
+bool launch(State& s, const Kind& k, uint64_t *v, Tally& tl)
+{
+    const uint32_t (*ob)[3] = k.ob;
+    const int distinct = k.distinct;
+    // ---- the library's side: the header's functions, called as rt_tracer.hip calls them
+    bool overlap = k.ask && distinct == 1 && s.t.any;
+    for (int i = 0; i < k.n && overlap; i++) overlap = rtk::fref_overlap_ok(s.f, ob[i]);
+    if (!overlap) rtk::fref_ordered(s.f);
+    // ---- the checker's side: which earlier launches may still run beside this one, and which of them
+    // this launch's stream waits for before its first kernel (order_overlap: the one before the last)
+    const uint32_t running = overlap ? s.t.last_reads : 0u;        // not waited for
+    const uint32_t waited = overlap ? s.t.prev_reads : 0u;         // in flight, but waited for
+    (void)waited;
+    tl.launches++;
+    tl.overlaps += overlap;
+    uint32_t used = 0, mine = 0;
+    int slot[3];
+    for (int i = 0; i < k.n; i++)
+    {
+        bool compute = false;
+        const int b = rtk::fref_slot_for_launch(s.f, ob[i], used, &compute);
+        if (b < 0)
+        {
+            v[overlap ? V_OVERLAP_NO_SLOT : V_NO_SLOT]++;
+            return false;
+        }
+        if (compute)
+        {
+            tl.recomputes++;
+            rtk::fref_computed(s.f, b, ob[i]);
+            // k_origin_pre into buffer b, in this launch's stream
+            if (running & (1u << b)) v[V_RUNNING]++;
+            if (mine & (1u << b)) v[V_SAME_LAUNCH]++;
+            // every launch in flight that reads b must be one order_overlap waits for
+            if (overlap && (s.t.last_reads & (1u << b))) v[V_MISSING_WAIT]++;
+            s.t.holds[b] = k.org[i];
+        }
+        used |= 1u << b;
+        mine |= 1u << b;
+        slot[i] = b;
+        if (s.t.holds[b] != k.org[i]) v[V_ORIGIN_AT_ISSUE]++;
+    }
+    for (int i = 0; i < k.n; i++)
+        if (s.t.holds[slot[i]] != k.org[i]) v[V_ORIGIN_AT_END]++;
+    rtk::fref_launched(s.f, used);
+    s.t.prev_reads = overlap ? s.t.last_reads : 0u;     // an ordered launch leaves nothing else in flight
+    s.t.last_reads = mine;
+    s.t.any = true;
+    return true;
+}
+
+void walk(const State& s, const std::vector<Kind>& kinds, int depth, int max_depth, const Kind **seq, Tally& tl)
+{
+    for (const Kind& k : kinds)
+    {
+        State n = s;
+        uint64_t v[V_KINDS] = {};
+        seq[depth] = &k;
+        const bool ok = launch(n, k, v, tl);
+        bool bad = false;
+        for (int i = 0; i < V_KINDS; i++)
+        {
+            tl.v[i] += v[i];
+            bad = bad || v[i];
+        }
+        if (bad && (!tl.short_len || depth + 1 < tl.short_len))
+        {
+            tl.short_len = depth + 1;
+            tl.short_seq = show(seq, depth + 1);
+        }
+        if (!ok || depth + 1 == max_depth)
+            tl.sequences++;
+        else
+            walk(n, kinds, depth + 1, max_depth, seq, tl);
+    }
+}
+
+} // namespace
+
+int main(int argc, char **argv)
+{
+    const int depth = argc > 1 ? std::atoi(argv[1]) : 4;
+    const int norg = argc > 2 ? std::atoi(argv[2]) : 4;
+    if (depth < 1 || depth > 8 || norg < 2 || norg > 8) return 2;
+    std::vector<Kind> kinds;
+    for (int ask = 0; ask < 2; ask++)
+    {
+        for (int a = 0; a < norg; a++) kinds.push_back(make_kind(1, a, 0, 0, ask != 0));
+        for (int a = 0; a < norg; a++)
+            for (int b = 0; b < norg; b++) kinds.push_back(make_kind(2, a, b, 0, ask != 0));
+        for (int a = 0; a < norg; a++)
+            for (int b = 0; b < norg; b++)
+            {
+                if (a == b) continue;
+                kinds.push_back(make_kind(3, a, a, b, ask != 0));
+                kinds.push_back(make_kind(3, a, b, a, ask != 0));
+                kinds.push_back(make_kind(3, b, a, a, ask != 0));
+            }
+    }
+    // one task per first launch, a few threads
+    std::vector<Tally> part(kinds.size());
+    std::mutex mtx;
+    size_t next = 0;
+    auto work = [&]() {
+        for (;;)
+        {
+            size_t i;
+            {
+                std::lock_guard<std::mutex> lk(mtx);
+                if (next >= kinds.size()) return;
+                i = next++;
+            }
+            State s;
+            s.t.holds[0] = s.t.holds[1] = -1;
+            s.t.last_reads = s.t.prev_reads = 0;
+            s.t.any = false;
+            const Kind *seq[8];
+            Tally tl;                           // (local: the tasks' tallies share cache lines)
+            // the first launch, then every continuation
+            State n = s;
+            uint64_t v[V_KINDS] = {};
+            seq[0] = &kinds[i];
+            const bool ok = launch(n, kinds[i], v, tl);
+            bool bad = false;
+            for (int q = 0; q < V_KINDS; q++)
+            {
+                tl.v[q] += v[q];
+                bad = bad || v[q];
+            }
+            if (bad)
+            {
+                tl.short_len = 1;
+                tl.short_seq = show(seq, 1);
+            }
+            if (!ok || depth == 1)
+                tl.sequences++;
+            else
+                walk(n, kinds, 1, depth, seq, tl);
+            part[i] = tl;
+        }
+    };
+    unsigned nt = std::thread::hardware_concurrency();
+    nt = nt < 1 ? 1 : (nt > 8 ? 8 : nt);
+    std::vector<std::thread> th;
+    for (unsigned i = 0; i < nt; i++) th.emplace_back(work);
+    for (std::thread& t : th) t.join();
+    Tally all;
+    for (const Tally& p : part)
+    {
+        all.sequences += p.sequences;
+        all.launches += p.launches;
+        all.overlaps += p.overlaps;
+        all.recomputes += p.recomputes;
+        for (int q = 0; q < V_KINDS; q++) all.v[q] += p.v[q];
+        if (p.short_len && (!all.short_len || p.short_len < all.short_len))
+        {
+            all.short_len = p.short_len;
+            all.short_seq = p.short_seq;
+        }
+    }
+    uint64_t total = 0;
+    for (int q = 0; q < V_KINDS; q++) total += all.v[q];
+    std::printf("{\"depth\": %d, \"origins\": %d, \"launch_kinds\": %zu, \"sequences\": %llu, \"launches\": %llu, "
+                "\"overlaps_granted\": %llu, \"recomputes\": %llu, \"violations\": %llu, \"by_kind\": {",
+                depth, norg, kinds.size(), (unsigned long long)all.sequences, (unsigned long long)all.launches,
+                (unsigned long long)all.overlaps, (unsigned long long)all.recomputes, (unsigned long long)total);
+    for (int q = 0; q < V_KINDS; q++)
+        std::printf("%s\"%s\": %llu", q ? ", " : "", kNames[q], (unsigned long long)all.v[q]);
+    std::printf("}, \"shortest_violating_sequence\": \"%s\"}\n", all.short_seq.c_str());
+    return 0;
+}
