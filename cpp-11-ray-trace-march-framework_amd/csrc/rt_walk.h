@@ -133,7 +133,8 @@ __device__ __forceinline__ uint32_t batch_frame(const KBatch& B, uint32_t b)
 }
 
 // CSR range of a cell: one u32 load of the packed (start << 11 | count) word when the scene
-// fits the packing (every scene of the reference does), else the two CSR offsets.
+// fits the packing (every scene of the reference does), else the two CSR offsets (a cell of
+// >= 2,048 references or >= 2^21 in all: tests/test_gpu_variants.py B1 walks that side).
 __device__ __forceinline__ void cell_range(const KParams& P, uint32_t cell, uint32_t& kb, uint32_t& ke)
 {
     if (P.cellw)

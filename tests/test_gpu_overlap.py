@@ -87,7 +87,8 @@ def _overlap_steps(golden, gss, sids, N, steps, check_every, hits_every=0):
 
 @pytest.mark.parametrize("N", [1, 2, 8])
 def test_overlap_bench_pair(golden, scenes, N):
-    """The bench pair (killeroo, Cornell) overlapped over 40 steps at N = 1 and over 36 steps of every
+    """Killeroo's and Cornell's frames in one batched launch per step (bench.py's pair; its plain run now
+    launches them as single frames, test_overlap_single_frames), overlapped over 40 steps at N = 1 and over 36 steps of every
     rank of 2 and 8 (the wide section fused in from 2 ranks): frames checked every 8 steps, hit IDs
     of a step in 8 -- through the measured frames (0, 1, 16, 32) and the plan adoptions."""
     sids = (8, 1)

@@ -260,9 +260,11 @@ def test_bary_full_frame_records(golden, scenes, sid):
 
 @pytest.mark.parametrize("nranks,overlap", [(1, True), (8, True), (8, False)], ids=["1", "8", "8-one-stream"])
 def test_moving_camera_views_batched(golden, nranks, overlap):
-    """bench.py's moving_camera leg pinned to the reference: the bench pair (killeroo first, bench.py's
-    order at one rank) orbiting 0.5 degrees per frame about the world y axis (bench.orbit_cam), 27
-    consecutive frames batched as the leg renders them -- fresh scenes, every frame a new origin
+    """bench.py's moving_camera cameras pinned to the reference: killeroo and the Cornell box (killeroo first)
+    orbiting 0.5 degrees per frame about the world y axis (bench.orbit_cam), 27 consecutive frames, each
+    step's two frames in one rt_render_batch_device launch (bench.py renders them batched only with its
+    batch option; its plain run launches single frames, which tests/test_gpu_origins.py and
+    test_gpu_overlap.py::test_overlap_single_frames cover) -- fresh scenes, every frame a new origin
     (k_origin_pre before its render) and a new view whose heavy-first order (and at a rank of 8 the wide
     section's list) is re-planned from the frame before (RT_HF_FOLLOW), consecutive steps overlapped on two
     streams into sentinel-filled buffers (one-stream: without RT_KERNEL_FLAG_OVERLAP, so a rank of 8's
