@@ -21,7 +21,7 @@
 //
 // Subcommands (all output little-endian binary files or one "RESULT {json}" line):
 //   dump-scenes <meshdir> <outdir>           post-setup meshes + cameras -> <outdir>/scene<i>.rtscene
-//   grid   <scene.rtscene> <out.bin>         grid meta + CSR export of Grid::Grid's cells
+//   grid   <scene.rtscene> <out.bin> [res]   grid meta + CSR export of Grid::Grid's cells (res: default 64)
 //   render <scene.rtscene> W H spp [--threads N] [--reps R] [--out f] [--hits f] [--bmp f]
 //                                            --bmp: the reference's WriteBitmap of the gathered frame
 //   samples <scene.rtscene> W H spp x0 y0 w h <out.bin>    per-sample records; refdriver_instr
@@ -832,14 +832,17 @@ int main(int argc, char **argv)
     if (cmd == "kat-dist" && argc == 3)
         return CmdKatDist(argv[2]);
 
-    if ((cmd == "grid" && argc == 4) || (cmd == "render" && argc >= 6) || (cmd == "samples" && argc >= 11) ||
-        (cmd == "alt-samples" && argc == 12))
+    if ((cmd == "grid" && (argc == 4 || argc == 5)) || (cmd == "render" && argc >= 6) ||
+        (cmd == "samples" && argc >= 11) || (cmd == "alt-samples" && argc == 12))
     {
         SceneFile sf;
         if (!ReadScene(argv[2], sf)) { std::fprintf(stderr, "bad scene file\n"); return 1; }
         const Mesh *mesh_ptr = sf.mesh.get();
+        // scene.cpp:6-7 builds with 64; "grid" takes another resolution (Grid::Grid's own parameter)
+        const uint grid_res = (cmd == "grid" && argc == 5) ? uint(std::atoi(argv[4])) : 64u;
+        if (grid_res == 0) return Usage();
         const double tb0 = TimerGetTick();
-        GridExport grid(std::move(sf.mesh), 64);                  // scene.cpp:6-7
+        GridExport grid(std::move(sf.mesh), grid_res);
         const double build_s = TimerGetTick() - tb0;
 
         if (cmd == "grid")
