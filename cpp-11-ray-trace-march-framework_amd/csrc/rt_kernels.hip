@@ -1020,9 +1020,10 @@ __global__ void __launch_bounds__(kWG) k_frame_tables(float *ndc, float2 *smp, T
 
 // Per-camera-origin records (kVarOriginPre): for CSR reference k, tvec = o - v0,
 // qvec = tvec x e1 and DOT(e2, qvec) exactly as triangle.h:82, 90, 98 compute them, in the
-// packed-pair layout of rtd::make_frec (64 B per reference).
-__global__ void __launch_bounds__(kWG) k_origin_pre(const float4 *refs, float4 *frefs, uint32_t n, float ox,
-                                                    float oy, float oz)
+// packed-pair layout of rtd::make_frec (64 B per reference).  With gates != null also the record's gate
+// record (rtk::make_gate, fp64, 32 B per reference) from the record's own e1, e2 and tvec.
+__global__ void __launch_bounds__(kWG) k_origin_pre(const float4 *refs, float4 *frefs, float4 *gates, uint32_t n,
+                                                    float ox, float oy, float oz)
 {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
@@ -1032,6 +1033,13 @@ __global__ void __launch_bounds__(kWG) k_origin_pre(const float4 *refs, float4 *
     frefs[4 * size_t(k) + 1] = f.r1;
     frefs[4 * size_t(k) + 2] = f.r2;
     frefs[4 * size_t(k) + 3] = f.r3;
+    if (gates)
+    {
+        float g[kGateFloats];
+        make_gate(r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, f.r0.y, f.r0.w, f.r1.y, g);
+        gates[2 * size_t(k) + 0] = make_float4(g[0], g[1], g[2], g[3]);
+        gates[2 * size_t(k) + 1] = make_float4(g[4], g[5], g[6], g[7]);
+    }
 }
 
 // Device KATs (rt_debug_primitives)

@@ -22,6 +22,15 @@ constexpr uint32_t kWavesPerWG = kWG / 64u;
 constexpr uint32_t kFrefPad = 2u * kWavesPerWG;
 // bytes of one per-origin record buffer of a scene with nrefs CSR references (64-byte records)
 constexpr size_t fref_buffer_bytes(uint32_t nrefs) { return (size_t(nrefs ? nrefs : 1u) + kFrefPad) * 64u; }
+// bytes of the gate array beside it (rt_record_gate.h: 32-byte gate records, the same zero pad -- the
+// gated loop loads gate records in pairs, up to two records past a list's end)
+constexpr size_t gate_buffer_bytes(uint32_t nrefs) { return (size_t(nrefs ? nrefs : 1u) + kFrefPad) * 32u; }
+// The wave-uniform record loop gates lists of this many records or more; shorter ones
+// (Cornell's: mostly hit) take the ungated loop.
+#ifndef RT_GATE_MIN_LIST       // (tools/build_variant.sh -DRT_GATE_MIN_LIST=n: the A/B arms)
+#define RT_GATE_MIN_LIST 8
+#endif
+constexpr uint32_t kGateMinList = RT_GATE_MIN_LIST;
 // Traversal features, combined into the VAR template argument of the render kernels.
 constexpr int kVarWaveGate = 2;             // skip a test's second half when no lane needs it
 constexpr int kVarSkipRun = 4;              // wave-uniform proven-empty runs in a tight loop
@@ -85,6 +94,7 @@ struct KParams
     uint32_t box_stride;        // words per copy (ncells)
     const float4 *refs;
     const float4 *frefs;        // per camera origin (kVarOriginPre), 3 float4 per reference
+    const float4 *gates;        // the records' gate records (2 float4 per reference), or null: no gate
     const float4 *shade;
     const float4 *face_n;
     const float4 *tri_mt;       // per triangle {v0, e1, e2} in triangle order (brute force)
@@ -256,7 +266,7 @@ kcfn_t compact_kernel(int tri, int var);       // k_render_compact<tri, var>(P, 
 kbfn_t batch_kernel(int var, bool w64, bool o8 = false);   // k_render_batch / _w64 / _w64_o8<MT, var>
 knfn_t trace_records_kernel();                 // k_trace_records(P, n)
 knfn_t record_fixup_kernel();                  // k_record_fixup(P, n)
-using origin_pre_fn = void (*)(const float4 *, float4 *, uint32_t, float, float, float);
+using origin_pre_fn = void (*)(const float4 *, float4 *, float4 *, uint32_t, float, float, float);
 using unshard_fn = void (*)(const uint32_t *, uint32_t *, uint32_t, uint32_t, uint32_t, uint32_t, uint64_t);
 using check_fn = void (*)(unsigned long long *);
 using primitives_fn = void (*)(int, const float *, uint32_t, float *);

@@ -105,6 +105,11 @@ struct rt_scene
     // in flight -- is waited for first (order_overlap).  fref: what each buffer holds and which ones the
     // last launch reads (rt_fref_slots.h, whose functions choose the buffer).
     float4 *d_frefs[2] = { nullptr, nullptr };
+    // The records' gate records (rt_record_gate.h, 32 B per reference, the same pad), one array beside
+    // each record buffer and written by the same k_origin_pre launch; rec_gate false (RT_REC_GATE=0 at
+    // rt_scene_create): the render kernels get no gate pointer and test every record.
+    float4 *d_gates[2] = { nullptr, nullptr };
+    bool rec_gate = true;
     rtk::FrefSlots fref;
     uint64_t *d_clk = nullptr;      // RT_KERNEL_FLAG_WAVE_CLOCK records of the last such launch
     size_t clk_cap = 0;

@@ -15,6 +15,8 @@
 //   frefs     float4[4*(R+pad)]   per camera origin (k_origin_pre), one 64-B record per CSR
 //                                 reference: the origin-only terms of triangle.h:82-98; then
 //                                 kFrefPad zero records (the uniform record loop's look-ahead)
+//   gates     float4[2*(R+pad)]   beside each frefs buffer (k_origin_pre), one 32-B gate record per
+//                                 CSR reference (rt_record_gate.h), the same zero pad
 //   shade     float4[3*T]         per triangle the 3 vertex normals (shading of a hit)
 //   face_n    float4[T]           face normal (IntersectRayTriBarycentric only)
 
@@ -414,6 +416,7 @@ void frame_params(const rt_scene *s, const rt_frame *f, KParams& P)
     P.box_stride = s->box_stride;
     P.refs = s->d_refs;
     P.frefs = s->d_frefs[0];                                    // ensure_origin_terms picks the buffer
+    P.gates = s->rec_gate ? s->d_gates[0] : nullptr;            // (and its gate array)
     P.shade = s->d_shade;
     P.face_n = s->d_facen;
     P.tri_mt = s->d_trimt;
@@ -460,7 +463,7 @@ bool fref_overlap_ok(const rt_scene *s, const float org[3])
 // launch per frame), ordered after every launch that may still read that buffer: the caller has ordered
 // st after the launch before the last one and -- unless this launch overlaps it, when its buffers count as
 // busy -- after the last one (order_all); busy: buffers that frames of this call read already.
-// Sets P.frefs and marks the buffer in *used.
+// Sets P.frefs (and P.gates, the buffer's gate array) and marks the buffer in *used.
 int ensure_origin_terms(rt_scene *s, KParams& P, hipStream_t st, uint32_t busy, uint32_t *used)
 {
     bool compute = false;
@@ -472,11 +475,13 @@ int ensure_origin_terms(rt_scene *s, KParams& P, hipStream_t st, uint32_t busy, 
     {
         if (s->nrefs)
             hipLaunchKernelGGL(origin_pre_kernel(), dim3((s->nrefs + kWG - 1) / kWG), dim3(kWG), 0, st, s->d_refs,
-                               s->d_frefs[b], s->nrefs, P.org[0], P.org[1], P.org[2]);
+                               s->d_frefs[b], s->rec_gate ? s->d_gates[b] : nullptr, s->nrefs, P.org[0], P.org[1],
+                               P.org[2]);
         RT_HIP(hipGetLastError());
         rtk::fref_computed(s->fref, b, ob);
     }
     P.frefs = s->d_frefs[b];
+    P.gates = s->rec_gate ? s->d_gates[b] : nullptr;
     *used |= 1u << b;
     return RT_OK;
 }
@@ -1110,6 +1115,7 @@ int rt_scene_create(const rt_scene_desc *d, int device, rt_scene **out)
     s->wh_lds = env_tunable("RT_WH_LDS", s->wh_lds);
     s->wh_beta16 = env_tunable("RT_WH_BETA16", s->wh_beta16);
     s->hf_follow = env_tunable("RT_HF_FOLLOW", s->hf_follow);
+    s->rec_gate = env_tunable("RT_REC_GATE", 1u) != 0u;         // 0: no record gate (the A/B arm)
     for (int a = 0; a < 3; a++)
     {
         s->dims[a] = g.dims[a];
@@ -1263,6 +1269,15 @@ int rt_scene_create(const rt_scene_desc *d, int device, rt_scene **out)
     RT_HIP(hipMalloc(&s->d_frefs[1], sizeof(float4) * nfrefs));
     RT_HIP(hipMemset(s->d_frefs[0], 0, sizeof(float4) * nfrefs));
     RT_HIP(hipMemset(s->d_frefs[1], 0, sizeof(float4) * nfrefs));
+    // their gate arrays (rt_record_gate.h), zeroed the same way: a zero gate record rejects nothing
+    // (the gated loop addresses a record by a 32-bit byte offset: no gate for a buffer of 4 GiB or more)
+    if (rtk::fref_buffer_bytes(nr) > 0xFFFFFFFFull) s->rec_gate = false;
+    const size_t ngates = rtk::gate_buffer_bytes(nr) / sizeof(float4);
+    for (int b = 0; b < 2; b++)
+    {
+        RT_HIP(hipMalloc(&s->d_gates[b], sizeof(float4) * ngates));
+        RT_HIP(hipMemset(s->d_gates[b], 0, sizeof(float4) * ngates));
+    }
     RT_HIP(hipMalloc(&s->d_shade, sizeof(float4) * shade.size()));
     RT_HIP(hipMalloc(&s->d_facen, sizeof(float4) * facen.size()));
     RT_HIP(hipMemcpy(s->d_off, g.cell_offsets, sizeof(uint32_t) * (nc + 1), hipMemcpyHostToDevice));
@@ -1352,7 +1367,7 @@ int rt_scene_create(const rt_scene_desc *d, int device, rt_scene **out)
         }
     }
     s->device_bytes = sizeof(uint32_t) * (nc + 1) +
-                      sizeof(float4) * (refs.size() + 2 * nfrefs + shade.size() + facen.size() + trimt.size() +
+                      sizeof(float4) * (refs.size() + 2 * nfrefs + 2 * ngates + shade.size() + facen.size() + trimt.size() +
                                         tridist.size() + distblk.size()) +
                       sizeof(uint32_t) * (cellw.size() + cellwo.size() + cellwb.size());
     RT_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
@@ -1402,6 +1417,8 @@ int rt_scene_destroy(rt_scene *s)
         (void)hipFree(s->d_refs);
         (void)hipFree(s->d_frefs[0]);
         (void)hipFree(s->d_frefs[1]);
+        (void)hipFree(s->d_gates[0]);
+        (void)hipFree(s->d_gates[1]);
         (void)hipFree(s->d_shade);
         (void)hipFree(s->d_facen);
         (void)hipFree(s->d_cellw);

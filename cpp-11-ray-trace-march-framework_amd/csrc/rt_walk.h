@@ -9,6 +9,7 @@
 
 #include "rt_device.h"
 #include "rt_kparams.h"
+#include "rt_record_gate.h"
 
 namespace rtk {
 namespace {
@@ -224,7 +225,7 @@ __device__ __forceinline__ bool test_cell(const KParams& P, float ox, float oy, 
     bool split = false;
     if constexpr (SPLIT) split = __any(ke - kb >= kLdsSplitMin);
     const uint32_t first = split ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0u, step = split ? kWavesPerWG : 1u;
-    const rtd::f2v ra = {dx, dy}, rc = {dy, dz};   // the ray as the record test's register pairs
+    rtd::f2v ra = {dx, dy}, rc = {dy, dz};         // the ray as the record test's register pairs
     // min(t, nct_ax) as a compare and select: neither is ever NaN (and -0 / +0 compare equal in
     // every later '<'), and fminf would canonicalise both operands first (2 more VALU per cell)
     const float tb0 = t < nct_ax ? t : nct_ax;
@@ -298,8 +299,91 @@ __device__ __forceinline__ bool test_cell(const KParams& P, float ox, float oy, 
                     // the set it is for, so that set is read after it and stays allocated until its
                     // load has returned (the last load's data is dropped).
                     const uint32_t n = ke0 - kb0;
-                    cvf4 *const endp = np + size_t(n >> 1) * 8u;
                     vf16 a, b;
+                    cvf4 *const cgates = (cvf4 *)P.gates;
+                    bool gated = false;             // wave-uniform
+                    if constexpr (!STATS) gated = n >= kGateMinList && cgates != nullptr;
+                    if (gated)
+                    {
+                        // The gated loop (rt_record_gate.h), for long lists (few of
+                        // whose records any lane's first half passes): the same pipeline over the
+                        // records' 32-byte gate records, a PAIR of them per 16-register set and one
+                        // vote per pair.  A lane the gate rejects fails the record's det / u test, so a
+                        // record every active lane rejects would leave every lane as it is: it is
+                        // skipped unloaded.  Any other record is loaded into the set its gate pair
+                        // came in -- the pair's compares have issued, the set is free until the next
+                        // gate load into it -- and takes test_rec unchanged, record a before record b:
+                        // the same hits in the same order.  The gate loads run up to three records past
+                        // the list's end, inside the gate array's zero pad (gate_buffer_bytes); a
+                        // record past the end is never tested (`two`).
+                        // The loop counts the list position k (of the set's first record) beside the
+                        // gate pointer, so a record's address is one shift away: crefs + (k << 6) as base
+                        // and 32-bit offset (the host passes a gate pointer only while the record buffer is
+                        // below 4 GiB).
+                        cvf4 *gp = cgates + size_t(kb0) * 2u;
+                        uint32_t k = kb0;
+                        const uint32_t kend = kb0 + (n & ~3u);
+                        auto gate_pair = [&](vf16& s, uint32_t ahead, bool two) {
+                            using rtd::f2v;
+                            // the direction from the ray's pairs, opaque here: the products then select
+                            // an element of the pair (op_sel), where loop-invariant (d, d) pairs would be
+                            // hoisted into six more VGPRs
+                            asm("" : "+v"(ra), "+v"(rc));
+                            const bool ja = gate_rejects(ra.x, ra.y, rc.y, f2v{s[0], s[1]}, f2v{s[2], s[3]},
+                                                         f2v{s[4], s[5]}, s[6]);
+                            const bool jb = gate_rejects(ra.x, ra.y, rc.y, f2v{s[8], s[9]}, f2v{s[10], s[11]},
+                                                         f2v{s[12], s[13]}, s[14]);
+                            const uint64_t ma = __builtin_amdgcn_ballot_w64(!ja);
+                            const uint64_t mb = two ? __builtin_amdgcn_ballot_w64(!jb) : 0ull;
+                            if ((ma | mb) != 0ull)
+                            {
+                                if (ma != 0ull)
+                                {
+                                    const uint32_t ro = (k + ahead) << 6;
+                                    asm volatile("s_load_dwordx16 %0, %1, %2" : "=&s"(s) : "s"(crefs), "s"(ro));
+                                    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(s));
+                                    test_rec(vf4{s[0], s[1], s[2], s[3]}, vf4{s[4], s[5], s[6], s[7]},
+                                             vf4{s[8], s[9], s[10], s[11]}, vf4{s[12], s[13], s[14], s[15]},
+                                             [&] { return k + ahead; });
+                                }
+                                if (mb != 0ull)
+                                {
+                                    const uint32_t ro = (k + ahead + 1u) << 6;
+                                    asm volatile("s_load_dwordx16 %0, %1, %2" : "=&s"(s) : "s"(crefs), "s"(ro));
+                                    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(s));
+                                    test_rec(vf4{s[0], s[1], s[2], s[3]}, vf4{s[4], s[5], s[6], s[7]},
+                                             vf4{s[8], s[9], s[10], s[11]}, vf4{s[12], s[13], s[14], s[15]},
+                                             [&] { return k + ahead + 1u; });
+                                }
+                            }
+                        };
+                        asm volatile("s_load_dwordx16 %0, %1, 0x0" : "=&s"(a) : "s"(gp));
+                        asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a));
+                        if (k != kend)
+                            do
+                            {
+                                asm volatile("s_load_dwordx16 %0, %1, 0x40" : "=&s"(b) : "s"(gp));
+                                gate_pair(a, 0u, true);
+                                asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(b));
+                                asm volatile("s_load_dwordx16 %0, %1, 0x80" : "=&s"(a) : "s"(gp));
+                                gate_pair(b, 2u, true);
+                                asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a));
+                                gp += 8;
+                                k += 4u;
+                                asm volatile("" : "+s"(gp), "+s"(k));   // two counters: neither derived from the other
+                            } while (k != kend);
+                        const uint32_t rem = n & 3u;
+                        if (rem != 0u)
+                        {
+                            asm volatile("s_load_dwordx16 %0, %1, 0x40" : "=&s"(b) : "s"(gp));
+                            gate_pair(a, 0u, rem >= 2u);
+                            asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(b));
+                            if (rem == 3u) gate_pair(b, 2u, false);
+                        }
+                    }
+                    else
+                    {
+                    cvf4 *const endp = np + size_t(n >> 1) * 8u;
                     asm volatile("s_load_dwordx16 %0, %1, 0x0" : "=&s"(a) : "s"(np));
                     asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(a));
                     if (np != endp)
@@ -322,6 +406,7 @@ __device__ __forceinline__ bool test_cell(const KParams& P, float ox, float oy, 
                         test_rec(vf4{a[0], a[1], a[2], a[3]}, vf4{a[4], a[5], a[6], a[7]},
                                  vf4{a[8], a[9], a[10], a[11]}, vf4{a[12], a[13], a[14], a[15]},
                                  [&] { return rec_k(np, 0u); });
+                    }
                 }
                 else
                 {
