@@ -15,6 +15,7 @@ pointers and streams then interoperate).  There is no CPU fallback: if a library
 call fails, :class:`RtError` is raised.  The directory name is not a Python identifier, so
 load it with :func:`load_package` from ``tests/``/``bench.py`` (importlib by path).
 """
+import collections
 import ctypes
 import os
 
@@ -24,7 +25,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # Everything librt_tracer.so is compiled from: PMC counter files are valid only for this hash
 KERNEL_SOURCES = ("csrc/rt_kernels.hip", "csrc/rt_walk.h", "csrc/rt_kparams.h", "csrc/rt_plan.hip",
                   "csrc/rt_scene.h", "csrc/rt_tracer.hip", "csrc/rt_grid_build.hip", "csrc/rt_device.h",
-                  "csrc/rt_internal.h", "csrc/rt_box_words.h", "csrc/rt_fref_slots.h", "csrc/rt_record_gate.h", "csrc/Makefile",
+                  "csrc/rt_internal.h", "csrc/rt_box_words.h", "csrc/rt_fref_slots.h", "csrc/rt_record_gate.h", "csrc/rt_rays.hip", "csrc/Makefile",
                   "../include/rt_tracer.h")
 
 
@@ -53,6 +54,7 @@ RT_KERNEL_COMPACT_REFILL_SHIFT = RT_KERNEL_BUDGET_SHIFT
 RT_ISECT_GRID = 0
 RT_ISECT_BRUTE_FORCE = 1
 RT_ISECT_RAY_MARCH = 2
+RT_RAYS_COUNT, RT_RAYS_SORT = 1, 2      # rt_trace_rays_device flags
 SHARD_TILE = 16
 
 # Symbols of include/rt_tracer.h and include/rt_host.h (checked by tests/test_abi.py)
@@ -65,6 +67,7 @@ TRACER_SYMBOLS = [
     "rt_scene_create_from_mesh", "rt_kernel_times", "rt_render_frame_host", "rt_frame_host_wait", "rt_host_alloc",
     "rt_host_free", "rt_render_hits_device", "rt_scene_info_get", "rt_build_hash", "rt_render_batch_device",
     "rt_render_records_device", "rt_render_frame_host_tiled", "rt_fref_buffer_bytes",
+    "rt_trace_rays_device", "rt_primary_rays_device",
 ]
 MAX_BATCH = 10                           # frames per rt_render_batch_device launch (kMaxBatch)
 
@@ -120,6 +123,14 @@ class Tile(ctypes.Structure):
     _fields_ = [("x0", c_u32), ("y0", c_u32), ("x1", c_u32), ("y1", c_u32)]
 
 
+class Ray(ctypes.Structure):                # rt_ray, 24 B
+    _fields_ = [("o", c_f32 * 3), ("d", c_f32 * 3)]
+
+
+class RayHit(ctypes.Structure):             # rt_ray_hit, 16 B
+    _fields_ = [("tri", c_u32), ("t", c_f32), ("u", c_f32), ("v", c_f32)]
+
+
 class SceneStats(ctypes.Structure):
     _fields_ = [("scene_id", c_u32), ("num_vertices", c_u32), ("num_triangles", c_u32),
                 ("num_cells", c_u32), ("num_refs", c_u32), ("max_refs_per_cell", c_u32),
@@ -138,6 +149,11 @@ class SceneInfo(ctypes.Structure):
 SAMPLE_REC_DTYPE = np.dtype([("hit", "<u4"), ("tri", "<u4"), ("voxel", "<u4"), ("steps", "<u4"),
                              ("tests", "<u4"), ("t", "<f4"), ("u", "<f4"), ("v", "<f4"),
                              ("r", "<f4"), ("g", "<f4"), ("b", "<f4"), ("pad", "<u4")])
+# rt_ray_hit (rt_trace_rays_device): a miss is tri 0xFFFFFFFF, t = u = v = 0
+RAY_HIT_DTYPE = np.dtype([("tri", "<u4"), ("t", "<f4"), ("u", "<f4"), ("v", "<f4")])
+RAY_WORDS, RAY_HIT_WORDS, SAMPLE_REC_WORDS = 6, 4, 12     # 32-bit words of rt_ray, rt_ray_hit, rt_sample_rec
+# GpuScene.trace_rays' result: per-ray columns, the raw rt_ray_hit words and (count=True) the records
+RayHits = collections.namedtuple("RayHits", ["tri", "t", "u", "v", "hits", "rec"])
 
 _tracer = None
 _host = None
@@ -187,6 +203,9 @@ def tracer_lib():
                                                    ctypes.POINTER(Tile), vp, vp]
         if hasattr(L, "rt_fref_buffer_bytes"):       # absent in earlier builds (A/B runs)
             L.rt_fref_buffer_bytes.argtypes = [c_u32, ctypes.POINTER(ctypes.c_uint64)]
+        if hasattr(L, "rt_trace_rays_device"):       # absent in earlier builds (A/B runs)
+            L.rt_trace_rays_device.argtypes = [vp, vp, c_u32, c_u32, vp, vp, vp]
+            L.rt_primary_rays_device.argtypes = [vp, ctypes.POINTER(Frame), vp, vp]
         L.rt_unshard_device.argtypes = [c_u32, c_u32, c_u32, vp, vp, vp]
         L.rt_last_kernel_ms.argtypes = [vp, ctypes.POINTER(c_f32)]
         L.rt_trace_samples.argtypes = [vp, ctypes.POINTER(Frame), c_u32, c_u32, c_u32, c_u32, vp]
@@ -660,6 +679,80 @@ class GpuScene:
         _check(L.rt_trace_samples(self._h, ctypes.byref(frame), x0, y0, w, h, _ptr(out)), L,
                "rt_trace_samples")
         return out
+
+    def _stream(self, torch, stream):
+        return torch.cuda.current_stream(self.device).cuda_stream if stream is None else int(stream)
+
+    def primary_rays(self, frame, stream=None):
+        """rt_primary_rays_device: the frame's width * height * spp camera rays in (y, x, sample) order
+        as a torch float32 [n, 6] tensor (origin, direction) on the scene's device -- the bits the frames
+        are traced with.  stream: a HIP stream handle (None: torch's current stream)."""
+        import torch
+        n = frame.width * frame.height * max(1, frame.spp)
+        rays = torch.empty((n, RAY_WORDS), dtype=torch.float32, device=f"cuda:{self.device}")
+        L = tracer_lib()
+        _check(L.rt_primary_rays_device(self._h, ctypes.byref(frame), ctypes.c_void_p(rays.data_ptr()),
+                                        ctypes.c_void_p(self._stream(torch, stream))), L, "rt_primary_rays_device")
+        return rays
+
+    def trace_rays(self, rays, count=False, sort=False, stream=None):
+        """rt_trace_rays_device: Grid::Intersect for caller-supplied rays [n, 6] (origin, direction; the
+        direction is used as passed, not normalised).
+
+        rays: a contiguous float32 torch CUDA tensor on the scene's device -- traced in place through
+        data_ptr(), asynchronously on `stream` (None: torch's current stream; with another stream the
+        outputs are marked as used on it, record_stream, and ordering `rays` and the readers of the results
+        against that stream is the caller's), results as torch tensors on that device -- or a C-contiguous float32
+        numpy array, which is uploaded, traced and the results downloaded (synchronous).  Anything else
+        (another dtype, shape, device, a strided view, a CPU tensor) raises ValueError before any launch.
+
+        Returns RayHits: tri u32 [n] (0xFFFFFFFF on a miss; int32 bits where torch has no uint32), t, u,
+        v f32 [n] (0 on a miss), hits = the raw [n, 4] words; with count=True (the counting walk,
+        RT_RAYS_COUNT) also rec: SAMPLE_REC_DTYPE records (numpy) / their int32 [n, 12] words (torch).
+        sort=True (RT_RAYS_SORT) traces the rays ordered by direction octant and entry cell -- for rays in no
+        useful order; the results are the same bits, in input order."""
+        import torch
+        host = isinstance(rays, np.ndarray)
+        if host:
+            if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != RAY_WORDS or not rays.flags["C_CONTIGUOUS"]:
+                raise ValueError("rays: a C-contiguous float32 array of shape [n, 6]")
+            d_rays = torch.from_numpy(rays).to(f"cuda:{self.device}")
+        elif isinstance(rays, torch.Tensor):
+            if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != RAY_WORDS:
+                raise ValueError("rays: a float32 tensor of shape [n, 6]")
+            if not rays.is_cuda or rays.device.index != self.device:
+                raise ValueError(f"rays: a tensor on cuda:{self.device} (host memory is not traced in place)")
+            if not rays.is_contiguous():
+                raise ValueError("rays: a contiguous tensor (a strided view would be read as other rays)")
+            d_rays = rays
+        else:
+            raise ValueError("rays: a torch CUDA tensor or a numpy array")
+        n = d_rays.shape[0]
+        dev = d_rays.device
+        hits = torch.empty((n, RAY_HIT_WORDS), dtype=torch.int32, device=dev)
+        rec = torch.empty((n, SAMPLE_REC_WORDS), dtype=torch.int32, device=dev) if count else None
+        flags = (RT_RAYS_COUNT if count else 0) | (RT_RAYS_SORT if sort else 0)
+        if stream is not None and int(stream) != torch.cuda.current_stream(dev).cuda_stream:
+            # the outputs come from torch's allocator on torch's current stream but are written on `stream`:
+            # tell the allocator, so a result dropped early is not handed out again while the kernel runs
+            ext = torch.cuda.ExternalStream(int(stream), device=dev)
+            for o in (hits, rec):
+                if o is not None:
+                    o.record_stream(ext)
+        L = tracer_lib()
+        _check(L.rt_trace_rays_device(self._h, ctypes.c_void_p(d_rays.data_ptr()), n, flags,
+                                      ctypes.c_void_p(hits.data_ptr()), ctypes.c_void_p(rec.data_ptr() if count else 0),
+                                      ctypes.c_void_p(self._stream(torch, stream))), L, "rt_trace_rays_device")
+        if host:
+            if stream is not None:
+                torch.cuda.synchronize(dev)            # the copies below run on torch's stream
+            h = hits.cpu().numpy().view(RAY_HIT_DTYPE).reshape(n)
+            r = rec.cpu().numpy().view(SAMPLE_REC_DTYPE).reshape(n) if count else None
+            return RayHits(h["tri"], h["t"], h["u"], h["v"], h, r)
+        u32 = getattr(torch, "uint32", None)
+        tri = hits[:, 0].view(u32) if u32 is not None else hits[:, 0]
+        return RayHits(tri, hits[:, 1].view(torch.float32), hits[:, 2].view(torch.float32),
+                       hits[:, 3].view(torch.float32), hits, rec)
 
     def close(self):
         if getattr(self, "_h", None):

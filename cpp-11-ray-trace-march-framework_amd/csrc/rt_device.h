@@ -148,6 +148,8 @@ __device__ __forceinline__ bool ray_tri_mt_pred(float ox, float oy, float oz, fl
 // ray_tri_mt_pred with a wave-uniform early out: when no active lane passes the det and u
 // checks (triangle.h:77-87) the q/v/t half is skipped for the whole wave.  A scalar branch
 // (s_cbranch on a ballot), not a divergent one; results identical to ray_tri_mt_pred.
+// FAST_RCP (rt_rays.hip only): inv_det by rcp_nr, as mt_rec_first -- the caller guarantees |det| < 2^126.
+template <bool FAST_RCP = false>
 __device__ __forceinline__ bool ray_tri_mt_gated(float ox, float oy, float oz, float dx, float dy, float dz,
                                                  float v0x, float v0y, float v0z,
                                                  float e1x, float e1y, float e1z,
@@ -158,7 +160,7 @@ __device__ __forceinline__ bool ray_tri_mt_gated(float ox, float oy, float oz, f
     const float py = dz * e2x - dx * e2z;
     const float pz = dx * e2y - dy * e2x;
     const float det = e1x * px + e1y * py + e1z * pz;
-    const float inv_det = 1.0f / det;
+    const float inv_det = FAST_RCP ? rcp_nr(det) : 1.0f / det;
     const float tx = ox - v0x, ty = oy - v0y, tz = oz - v0z;
     u = (tx * px + ty * py + tz * pz) * inv_det;
     const bool ok1 = !(det > -0.00000001f && det < 0.00000001f) & !(u < 0.0f || u > 1.0f);

@@ -435,13 +435,13 @@ int exclusive_scan(BuildBuffers& B, ScanLevels& L, const Tin *in, Tout *out, uin
 }
 
 // Sorts n keys by their low `bits` bits; *sorted = the buffer (a or b) that holds the result.
+// counts / offs: 256 words per 1,024-key tile each (null: allocated here, for this sort)
 int radix_sort(BuildBuffers& B, ScanLevels& L, unsigned long long *a, unsigned long long *b, uint32_t n,
-               uint32_t bits, unsigned long long **sorted)
+               uint32_t bits, unsigned long long **sorted, uint32_t *counts = nullptr, uint32_t *offs = nullptr)
 {
     const uint32_t nb = (n + kRsTile - 1) / kRsTile;
-    uint32_t *counts, *offs;
-    RG_HIP(B.alloc(&counts, size_t(256) * nb));
-    RG_HIP(B.alloc(&offs, size_t(256) * nb));
+    if (!counts) RG_HIP(B.alloc(&counts, size_t(256) * nb));
+    if (!offs) RG_HIP(B.alloc(&offs, size_t(256) * nb));
     for (uint32_t shift = 0; shift < bits; shift += 8)
     {
         hipLaunchKernelGGL(k_rs_count, dim3(nb), dim3(kRsBlock), 0, B.st, a, n, shift, counts);
@@ -572,6 +572,53 @@ int build(const rt_vertex *v, uint32_t nv, const rt_triangle *t, uint32_t nt, ui
 }
 
 } // namespace
+
+// ---- the radix sort for the other translation units (rt_internal.h) ----
+// Every buffer lives in B and is freed with the scratch; B.st is the caller's stream of the current
+// sort (never owned: cleared before B goes, so ~BuildBuffers neither waits on nor destroys it).
+struct rt_sort_scratch
+{
+    BuildBuffers B;
+    ScanLevels L;
+    unsigned long long *a = nullptr, *b = nullptr;
+    uint32_t *counts = nullptr, *offs = nullptr;
+    uint32_t cap = 0;                   // keys a and b hold
+};
+
+void rt_internal_sort_free(rt_sort_scratch *sc)
+{
+    if (!sc) return;
+    sc->B.st = nullptr;
+    delete sc;
+}
+
+int rt_internal_sort_reserve(rt_sort_scratch **scp, uint32_t n, unsigned long long **keys)
+{
+    if (!*scp || (*scp)->cap < n)
+    {
+        rt_internal_sort_free(*scp);
+        *scp = nullptr;
+        rt_sort_scratch *sc = new rt_sort_scratch;
+        *scp = sc;                      // (a failed allocation below leaves cap = 0: the next call starts over)
+        const uint32_t nb = (n + kRsTile - 1) / kRsTile;
+        RG_HIP(sc->B.alloc(&sc->a, n));
+        RG_HIP(sc->B.alloc(&sc->b, n));
+        RG_HIP(sc->B.alloc(&sc->counts, size_t(256) * nb));
+        RG_HIP(sc->B.alloc(&sc->offs, size_t(256) * nb));
+        sc->cap = n;
+    }
+    *keys = (*scp)->a;
+    return RT_OK;
+}
+
+int rt_internal_sort_run(rt_sort_scratch *sc, hipStream_t st, uint32_t n, uint32_t bits, unsigned long long **sorted)
+{
+    if (!sc || n == 0 || n > sc->cap) return rt_internal_fail(RT_E_INVALID, "internal: sort scratch not reserved");
+    sc->B.st = st;
+    const int rc = radix_sort(sc->B, sc->L, sc->a, sc->b, n, bits, sorted, sc->counts, sc->offs);
+    sc->B.st = nullptr;
+    return rc;
+}
 
 extern "C" {
 

@@ -49,6 +49,9 @@ constexpr int kVarWideFused = 1048576;      // batch kernel: the wide section's 
 constexpr int kVarWideG4 = 2097152;         // the wide section at 4 lanes per sample (spp 8-16; else 16)
 constexpr int kVarLdsSplit = 4194304;       // the wide section's LDS tier: the waves of a workgroup split one
                                             // item's cell lists, reduced through LDS (wide_section_lds)
+constexpr int kVarRays = 8388608;           // rt_trace_rays_device (rt_rays.hip): caller-supplied rays, one per
+                                            // lane and unrelated to their neighbours -- the box-run walk stays in
+                                            // its per-lane phase and the record test reads the 48-byte refs
 // AUTO's traversal: every feature above that is exact for every scene ...
 constexpr int kVarAutoCore = kVarWaveGate | kVarDistSkip | kVarOriginPre | kVarXcdBands | kVarUniform;
 // ... plus the two that need a scene property (rt_scene::rcp_safe, rt_scene::pack_ok)
@@ -277,5 +280,15 @@ unshard_fn unshard_kernel();
 check_fn rcp_check_kernel();
 check_fn gamma_check_kernel();
 primitives_fn primitives_kernel();
+// rt_rays.hip: k_trace_rays<var, count>(P, rays, order, n, hits, recs) -- var: kVarRays | kVarWaveGate | kVarDistSkip |
+// the scene's traversal bits (rt_tracer.hip scene_traversal_bits); count: the counting walk (var 0) -- and
+// k_primary_rays(P, rays, n).  A getter returns nullptr for a variant that is not built.
+using rays_fn = void (*)(KParams, const float2 *, const unsigned long long *, uint32_t, rt_ray_hit *, rt_sample_rec *);
+using ray_keys_fn = void (*)(KParams, const float2 *, uint32_t, uint32_t, unsigned long long *);
+using primary_fn = void (*)(KParams, float2 *, uint32_t);
+rays_fn trace_rays_kernel(int var, bool count);
+primary_fn primary_rays_kernel();
+ray_keys_fn ray_keys_kernel();                  // k_ray_keys(P, rays, n, shift, keys): RT_RAYS_SORT's sort words
+uint32_t ray_key_bits();                        // ... which are sorted by this many low bits
 
 } // namespace rtk

@@ -209,6 +209,12 @@ struct rt_scene
     // RT_KERNEL_FLAG_WIDE_HEAVY: side stream of the wide section, fork / join events
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    // rt_trace_rays_device with RT_RAYS_SORT: the sort's scratch (keys, counts; grown only when n grows),
+    // shared by the scene's sorted calls -- a call on another stream than the last one waits for rays_ev
+    rt_sort_scratch *rays_sort = nullptr;
+    hipEvent_t rays_ev = nullptr;
+    hipStream_t rays_stream = nullptr;
+    bool rays_ev_recorded = false;
     // staging for rt_render_tiles / records
     uint32_t *d_frame = nullptr;
     size_t frame_cap = 0;

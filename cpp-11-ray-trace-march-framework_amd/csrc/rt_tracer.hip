@@ -157,6 +157,13 @@ bool auto_runs(const rt_scene *s)
     return s->pack_ok && s->box_words;
 }
 
+// The traversal features that need a scene property, for the render launches (on top of kVarAutoCore)
+// and for rt_trace_rays_device (on top of kVarRays): one table serves both paths.
+int scene_traversal_bits(const rt_scene *s)
+{
+    return (s->rcp_safe ? kVarFastRcp : 0) | (auto_runs(s) ? kVarPackedRem | kVarSkipRun : 0);
+}
+
 int ensure_device(const rt_scene *s)
 {
     int cur = -1;
@@ -379,6 +386,8 @@ int validate_frame(const rt_frame *f)
     return RT_OK;
 }
 
+void scene_params(const rt_scene *s, KParams& P);
+
 // Fills the per-frame parameters (camera constants exactly as camera.h computes them).
 void frame_params(const rt_scene *s, const rt_frame *f, KParams& P)
 {
@@ -398,6 +407,15 @@ void frame_params(const rt_scene *s, const rt_frame *f, KParams& P)
     P.spp_shift = is_pow2(P.spp) ? log2u(P.spp) : 0;
     P.inv_spp = is_pow2(P.spp) ? 1.0f / float(P.spp) : 0.0f;
     P.smp = s->d_smp;
+    scene_params(s, P);
+    P.tri_test = f->tri_test;
+    P.isect = f->intersector;
+}
+
+// The scene's own arrays and grid constants (frame_params' second half; rt_trace_rays_device fills
+// nothing else)
+void scene_params(const rt_scene *s, KParams& P)
+{
     for (int a = 0; a < 3; a++)
     {
         P.bmin[a] = s->bmin[a];
@@ -430,8 +448,6 @@ void frame_params(const rt_scene *s, const rt_frame *f, KParams& P)
         P.smax[a] = s->vmax[a];
     }
     P.ntris = s->ntris;
-    P.tri_test = f->tri_test;
-    P.isect = f->intersector;
 }
 
 bool use_lanes(const rt_frame *f, uint32_t spp)
@@ -522,7 +538,7 @@ int launch_render(rt_scene *s, const rt_frame *f, KParams& P, uint32_t n_local_t
         !auto_wide(s, P) && P.spp <= 64u && !s->tab_dirty)
     {
         overlap = fref_overlap_ok(s, P.org);
-        const int v = kVarAutoCore | (s->rcp_safe ? kVarFastRcp : 0) | (auto_runs(s) ? kVarPackedRem | kVarSkipRun : 0);
+        const int v = kVarAutoCore | scene_traversal_bits(s);
         if (overlap && blocks >= s->hf_min_blocks)
         {
             const HfPeek pk = hf_peek(s, P, blocks, v, 0u, cam_signature(P));
@@ -550,8 +566,7 @@ int launch_render(rt_scene *s, const rt_frame *f, KParams& P, uint32_t n_local_t
     int var = 0;
     if (auto_path)
     {
-        var = kVarAutoCore | (s->rcp_safe ? kVarFastRcp : 0) | (auto_runs(s) ? kVarPackedRem | kVarSkipRun : 0) |
-              ((f->kernel & RT_KERNEL_FLAG_WAVE_CLOCK) ? kVarWaveClock : 0);
+        var = kVarAutoCore | scene_traversal_bits(s) | ((f->kernel & RT_KERNEL_FLAG_WAVE_CLOCK) ? kVarWaveClock : 0);
         uint32_t used = 0;
         if (int rc = ensure_origin_terms(s, P, st, 0u, &used)) return rc;
         rtk::fref_launched(s->fref, used);
@@ -754,8 +769,7 @@ int launch_batch(rt_scene *const *S, const rt_frame *F, uint32_t n, KParams *P, 
         if (P[i].isect != RT_ISECT_GRID || P[i].tri_test != RT_TRI_MOLLER_TRUMBORE) return RT_E_INVALID;
         if (P[i].W != P[0].W || P[i].H != P[0].H || P[i].spp != spp || S[i]->device != S[0]->device)
             return RT_E_INVALID;
-        const int v = kVarAutoCore | (S[i]->rcp_safe ? kVarFastRcp : 0) |
-                      (auto_runs(S[i]) ? kVarPackedRem | kVarSkipRun : 0);
+        const int v = kVarAutoCore | scene_traversal_bits(S[i]);
         if (var >= 0 && v != var) return RT_E_INVALID;
         var = v;
         wide_heavy = wide_heavy || (F[i].kernel & RT_KERNEL_FLAG_WIDE_HEAVY) ||
@@ -1435,6 +1449,9 @@ int rt_scene_destroy(rt_scene *s)
             if (h.fence_ev) (void)hipEventDestroy(h.fence_ev);
         }
         if (s->h_wh_cnt) (void)hipHostFree(s->h_wh_cnt);
+        if (s->rays_ev_recorded) (void)hipEventSynchronize(s->rays_ev);
+        rt_internal_sort_free(s->rays_sort);
+        if (s->rays_ev) (void)hipEventDestroy(s->rays_ev);
         if (s->side) (void)hipStreamDestroy(s->side);
         if (s->plan_st) (void)hipStreamDestroy(s->plan_st);
         if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
@@ -2005,6 +2022,99 @@ int rt_trace_samples(rt_scene *s, const rt_frame *f, uint32_t x0, uint32_t y0, u
     if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
     (void)hipFree(d_rec);
     if (e != hipSuccess) return fail(RT_E_HIP, std::string("rt_trace_samples: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
+// Every argument is checked before the scene is touched.  Without RT_RAYS_SORT no lock and no events: the
+// launch reads only what rt_scene_create wrote (scene_params), so it is ordered against nothing but its
+// own stream.
+int rt_trace_rays_device(rt_scene *s, const rt_ray *d_rays, uint32_t n, uint32_t flags, rt_ray_hit *d_hits,
+                         rt_sample_rec *d_recs, void *hip_stream)
+{
+    if (!s) return fail(RT_E_INVALID, "scene is NULL");
+    if (flags & ~uint32_t(RT_RAYS_COUNT | RT_RAYS_SORT)) return fail(RT_E_INVALID, "unknown rt_rays_flags bit");
+    const bool count = (flags & RT_RAYS_COUNT) != 0u, sort = (flags & RT_RAYS_SORT) != 0u;
+    if (count && !d_recs) return fail(RT_E_INVALID, "RT_RAYS_COUNT needs d_recs");
+    if (!count && d_recs) return fail(RT_E_INVALID, "d_recs without RT_RAYS_COUNT");
+    if (n >= 0x80000000u) return fail(RT_E_INVALID, "n must be below 2^31");
+    if (n == 0) return RT_OK;
+    if (!d_rays) return fail(RT_E_INVALID, "d_rays is NULL");
+    if (!count && !d_hits) return fail(RT_E_INVALID, "d_hits is NULL");
+    if ((uintptr_t(d_rays) | uintptr_t(d_hits) | uintptr_t(d_recs)) & 7u)
+        return fail(RT_E_INVALID, "d_rays, d_hits and d_recs must be 8-byte aligned");
+    if (int rc = ensure_device(s)) return rc;
+    KParams P;
+    std::memset(&P, 0, sizeof(P));
+    scene_params(s, P);
+    P.frefs = nullptr;                  // per-camera-origin state: not this path's
+    P.gates = nullptr;
+    // the fast arm's walk: the box runs where the scene has them, else the octant distance skip (a scene
+    // without packed cell words walks the plain CSR ranges: grid_intersect tests P.cellw)
+    const int var = kVarRays | kVarWaveGate | kVarDistSkip | scene_traversal_bits(s);
+    const rays_fn fn = trace_rays_kernel(var, count);
+    if (!fn) return fail(RT_E_INVALID, "kernel variant not built: " + std::to_string(var));
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const float2 *rays = reinterpret_cast<const float2 *>(d_rays);
+    const dim3 grid((n + kWG - 1) / kWG), wg(kWG);
+    if (!sort)
+    {
+        hipLaunchKernelGGL(fn, grid, wg, 0, st, P, rays, static_cast<const unsigned long long *>(nullptr), n, d_hits,
+                           d_recs);
+        RT_HIP(hipGetLastError());
+        return RT_OK;
+    }
+    // RT_RAYS_SORT: sort words (k_ray_keys) -> the grid build's radix sort -> the same trace kernel reading
+    // its rays through the sorted words.  The scratch is the scene's and is the one piece of state this
+    // path has: sorted calls are serialised by the scene's mutex, and one on another stream than the last
+    // waits for it (rays_ev).  It grows -- a free and an allocation, which wait for the device -- only when
+    // n exceeds every earlier sorted n.
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (!s->rays_ev) RT_HIP(hipEventCreateWithFlags(&s->rays_ev, s->ev_order_flags));
+    if (s->rays_ev_recorded && st != s->rays_stream) RT_HIP(hipStreamWaitEvent(st, s->rays_ev, 0));
+    unsigned long long *keys = nullptr, *sorted = nullptr;
+    if (int rc = rt_internal_sort_reserve(&s->rays_sort, n, &keys)) return rc;
+    // cells per axis beyond 512 drop their low bits from the key (9 bits an axis)
+    uint32_t shift = 0;
+    while ((std::max(std::max(s->dims[0], s->dims[1]), s->dims[2]) - 1u) >> shift >= 512u) shift++;
+    hipLaunchKernelGGL(ray_keys_kernel(), grid, wg, 0, st, P, rays, n, shift, keys);
+    RT_HIP(hipGetLastError());
+    if (int rc = rt_internal_sort_run(s->rays_sort, st, n, ray_key_bits(), &sorted)) return rc;
+    hipLaunchKernelGGL(fn, grid, wg, 0, st, P, rays, static_cast<const unsigned long long *>(sorted), n, d_hits, d_recs);
+    RT_HIP(hipGetLastError());
+    RT_HIP(hipEventRecord(s->rays_ev, st));
+    s->rays_stream = st;
+    s->rays_ev_recorded = true;
+    return RT_OK;
+}
+
+int rt_primary_rays_device(rt_scene *s, const rt_frame *f, rt_ray *d_rays, void *hip_stream)
+{
+    if (!s || !d_rays) return fail(RT_E_INVALID, "NULL argument");
+    if (uintptr_t(d_rays) & 7u) return fail(RT_E_INVALID, "d_rays must be 8-byte aligned");
+    int rc = validate_frame(f);
+    if (rc) return rc;
+    const uint32_t spp = std::max(1u, f->spp);
+    const uint64_t n64 = uint64_t(f->width) * f->height * spp;
+    if (n64 >= 0x80000000ull) return fail(RT_E_INVALID, "more than 2^31 - 1 rays");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if ((rc = ensure_device(s))) return rc;
+    if ((rc = prepare_samples(s, f, spp))) return rc;
+    KParams P;
+    frame_params(s, f, P);
+    // a launch of the scene that reads its frame tables: after every launch that may still read the old
+    // ones, and itself the scene's last launch (as launch_render's plain arms)
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if ((rc = order_all(s, st))) return rc;
+    if ((rc = flush_tables(s, st))) return rc;
+    s->last_stream = st;
+    rtk::fref_launched(s->fref, 0u);            // (this launch reads no per-origin records)
+    const uint32_t n = uint32_t(n64);
+    hipLaunchKernelGGL(primary_rays_kernel(), dim3((n + kWG - 1) / kWG), dim3(kWG), 0, st, P,
+                       reinterpret_cast<float2 *>(d_rays), n);
+    RT_HIP(hipGetLastError());
+    RT_HIP(hipEventRecord(s->ev_own->ev, st));
+    s->ev_last = s->ev_own;
+    s->ev_recorded = true;
     return RT_OK;
 }
 

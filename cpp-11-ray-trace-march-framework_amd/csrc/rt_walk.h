@@ -462,8 +462,10 @@ __device__ __forceinline__ bool test_cell(const KParams& P, float ox, float oy, 
                                          r1.y, r1.z, r1.w, r2.x, fn.x, fn.y, fn.z, ct, cu, cv);
         }
         else if (VAR & kVarWaveGate)
-            hit = rtd::ray_tri_mt_gated(ox, oy, oz, dx, dy, dz, r0.x, r0.y, r0.z, r0.w, r1.x,
-                                        r1.y, r1.z, r1.w, r2.x, ct, cu, cv);
+            // (kVarRays: per-lane origins, so the 48-byte records and the whole test per ray; the vote
+            // is exact for any set of lanes)
+            hit = rtd::ray_tri_mt_gated<F && (VAR & kVarRays) != 0>(ox, oy, oz, dx, dy, dz, r0.x, r0.y, r0.z, r0.w, r1.x,
+                                                                    r1.y, r1.z, r1.w, r2.x, ct, cu, cv);
         else
             hit = rtd::ray_tri_mt_pred(ox, oy, oz, dx, dy, dz, r0.x, r0.y, r0.z, r0.w, r1.x,
                                        r1.y, r1.z, r1.w, r2.x, ct, cu, cv);
@@ -814,6 +816,18 @@ __device__ __forceinline__ bool grid_intersect(const KParams& P, float ox, float
                 ke = kb + (w & ne & 2047u);
                 boxw = int(w & ~ne);
             }
+            // kVarRays (rt_rays.hip: a caller's rays, which need not share cells): the lane stays in the
+            // per-lane phase for the whole walk -- it never waits at its first non-empty cell (a parked lane
+            // would idle behind 63 unrelated walks) and never enters lock-step; `sync` stays false.
+            // No input can hang or misdirect this loop: `cell` is dda_setup's clamped start cell plus the
+            // ray's copy offset (box_offset: octant < 8, major axis < 3) plus steps, and every step along
+            // axis a takes a unit from that axis' remaining-cell count in remp, which started at the cells
+            // left to the grid's face and ends the walk when it borrows -- so `cell` never leaves the ray's
+            // copy of the grid, whatever the crossing times hold (NaN and inf included: they only choose
+            // WHICH axis steps).  A per-lane run moves at most the box's own counts (each add chain is
+            // bounded by its field, the bare steps by the borrow), and a box is clipped to the grid.  Every
+            // record index [kb, ke) comes from a cell word.  Nothing is indexed by a value of the ray.
+            if constexpr ((VAR & kVarRays) == 0)
             if (!sync)
             {
                 // Approach: a lane at its first non-empty cell waits there (no step, no test; the

@@ -286,6 +286,47 @@ int  rt_render_records_device(rt_scene *const *scenes, const rt_frame *frames, u
                               uint32_t nranks, uint32_t *const *d_outs, const rt_tile *rects,
                               rt_sample_rec *const *d_recs, void *hip_stream);
 
+/* ---- ray queries ---------------------------------------------------------------------
+ * Grid::Intersect (grid.cpp:159-281) for rays the CALLER supplies -- a second bounce, shadow or
+ * ambient-occlusion rays, picking, baking -- instead of the camera's. */
+typedef struct rt_ray     { float o[3]; float d[3]; } rt_ray;          /* 24 B: Grid::Intersect's (origin, dir) */
+typedef struct rt_ray_hit { uint32_t tri; float t, u, v; } rt_ray_hit;  /* 16 B; miss: tri 0xFFFFFFFF, t = u = v = 0 */
+enum rt_rays_flags {
+    RT_RAYS_COUNT = 1,   /* the plain counting walk (the walk of rt_trace_samples); fills d_recs */
+    RT_RAYS_SORT = 2,    /* trace the rays in the order of (direction octant, Morton code of the entry cell), so
+                            that a wave's rays start together: for rays in no useful order (shuffled, a
+                            bounce).  Results are bit-identical and land in input order.  The sort runs on
+                            hip_stream inside the call, over scratch kept on the scene (grown, with a device
+                            wait, only when n exceeds every earlier sorted n; sorted calls of one scene are
+                            serialised and ordered after each other).  DESIGN.md §4.27 */
+};
+/* Ray i of d_rays[0, n) gives exactly what Grid::Intersect(o, d, t, u, v, tri_idx) with IntersectRayTri
+ * (triangle.h:15-107) gives on this scene's grid: d is used as passed (NOT normalised), every cell's list
+ * is tested in the reference's order and the strict '<' keeps the first of equal t.  d_hits[i] receives
+ * the result, in input order.  Asynchronous on hip_stream.  Without RT_RAYS_SORT it never waits on the host,
+ * allocates nothing, takes no lock, and reads only the scene's immutable arrays (cell words, CSR offsets,
+ * triangle records): it needs no ordering against render launches of the same scene and touches none of
+ * their state.  With RT_RAYS_SORT the call is still asynchronous and touches no render state, but it has
+ * state of its own: it takes the scene's mutex (which the scene's render calls also take, for the length of
+ * their host-side launch code), and it allocates -- hipFree / hipMalloc, which wait for the device -- when n
+ * exceeds every earlier sorted n of the scene (the key buffers at once, the sort's scan buffers in the first
+ * sort after that).
+ *   n == 0: RT_OK, nothing written.  n < 2^31.  d_rays / d_hits / d_recs: device memory on the scene's
+ *   device, 8-byte aligned (NULL or misaligned: RT_E_INVALID).
+ *   RT_RAYS_COUNT: needs d_recs; d_recs[i] = hit, tri, voxel (GridIdx of the accepted cell / of the last
+ *   cell walked; 0xFFFFFFFF when the ray misses the grid box), steps, tests, t, u, v as rt_trace_samples
+ *   counts them; r = g = b = 0, pad = 0.  d_hits may then be NULL.  Without the flag d_recs must be NULL.
+ *   A ray with any non-finite component (NaN, +-inf) is a miss without a walk: tri 0xFFFFFFFF, t = u = v =
+ *   0, and in a record hit 0, voxel 0xFFFFFFFF, steps = tests = 0.  The reference's behaviour there is
+ *   undefined (a float -> int conversion of NaN, grid.h:46), so this is a definition, not a deviation. */
+int  rt_trace_rays_device(rt_scene *scene, const rt_ray *d_rays, uint32_t n, uint32_t flags,
+                          rt_ray_hit *d_hits, rt_sample_rec *d_recs, void *hip_stream);
+/* The frame's width * height * spp camera rays in (y, x, sample) order into d_rays: origin and direction
+ * exactly as the render kernels form them (GenerateRay, camera.h:8-47, over the frame's tables), i.e. the
+ * bits the frames are traced with -- the start of a bounce.  A launch of the scene like a render call
+ * (it may rewrite the scene's frame tables), asynchronous on hip_stream. */
+int  rt_primary_rays_device(rt_scene *scene, const rt_frame *frame, rt_ray *d_rays, void *hip_stream);
+
 /* Render-kernel time of the last timed rendering call on this scene (ms): the HIP events on the
  * launch stream immediately around its render kernel(s), as rt_kernel_times.  Waits for them. */
 int  rt_last_kernel_ms(rt_scene *scene, float *ms);

@@ -1,0 +1,204 @@
+#!/usr/bin/env python3
+"""Measures rt_trace_rays_device (GpuScene.trace_rays) on scenes 8 and 1 at 1920x1080x4 and writes
+profiles/rays_bench.json (with the loaded library's rt_build_hash).
+
+Legs, each in rays/s between HIP events on the launch stream -- 0.2 s of the leg's own launches to bring the
+clocks up (as bench.py does), `--warmup` launches, then the median of 5 samples of `--steps` launches and the
+spread (max - min) / median of the five:
+  (a) camera order: the frame's rays from primary_rays, next to render_frame_device's samples/s for the same
+      frame from the PARENT build (--parent-lib, a librt_tracer.so of the parent commit in the package
+      directory) and from this build, same session, and the ratio -- the price of per-lane origins and 48-byte
+      records against the per-camera-origin records;
+  (b) the same rays shuffled with PCG64(41);
+  (c) one ambient-occlusion bounce: 4 seeded hemisphere rays per primary hit, from the hit point pushed off
+      the surface;
+  (d) (b) and (c) with RT_RAYS_SORT, the sort's own kernels inside the timed span (arm `this_sorted` of those
+      legs; `d_sort` holds the comparison, and the sorted call on camera-order rays, where it can only cost).
+--ab-lib NAME=LIB adds the same legs from another build of the library in the package directory (how the
+lock-step walk was measured, profiles/rays_walk_ab.json), samples interleaved with this build's, and checks
+that its results are the same bits.
+
+    python3 tools/bench_rays.py --parent-lib librt_tracer_parent.so [--ab-lib other=librt_tracer_other.so]
+"""
+import argparse
+import importlib.util
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch  # first: share torch's HIP runtime
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+INIT = os.path.join(ROOT, "cpp-11-ray-trace-march-framework_amd", "__init__.py")
+W, H, SPP = 1920, 1080, 4
+AO_PER_HIT = 4
+AO_OFFSET = 1e-4            # of the grid's largest extent: the bounce origin's push along the facing normal
+
+
+def load(name, lib):
+    if lib:
+        os.environ["RT_TRACER_LIB"] = lib
+    spec = importlib.util.spec_from_file_location(name, INIT)
+    m = importlib.util.module_from_spec(spec)
+    sys.modules[name] = m
+    spec.loader.exec_module(m)
+    m.tracer_lib()
+    m.host_lib()
+    os.environ.pop("RT_TRACER_LIB", None)
+    return m
+
+
+def sample(fn, steps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(steps):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / steps            # ms per launch
+
+
+def warm(fn, warmup, clock_warmup=0.2):
+    t_end = time.perf_counter() + clock_warmup
+    while time.perf_counter() < t_end:
+        fn()
+        torch.cuda.synchronize()
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+
+
+def measure(fns, n_items, steps, warmup):
+    """fns: {arm: callable}; samples interleaved over the arms.  Per arm: median ms, items/s, spread."""
+    for fn in fns.values():
+        warm(fn, warmup)
+    ms = {k: [] for k in fns}
+    for _ in range(5):
+        for k, fn in fns.items():
+            ms[k].append(sample(fn, steps))
+    out = {}
+    for k, v in ms.items():
+        med = float(np.median(v))
+        out[k] = {"ms": round(med, 4), "per_s": round(n_items / (med * 1e-3), 1),
+                  "spread": round((max(v) - min(v)) / med, 4), "samples_ms": [round(x, 4) for x in v]}
+    return out
+
+
+def ao_rays(rays, hits, tri_n, ext, seed=43):
+    """4 seeded directions in the hemisphere of the hit triangle's face normal turned against the incoming
+    ray, from the hit point pushed AO_OFFSET * ext along that normal (torch, on the device)."""
+    g = torch.Generator(device=rays.device)
+    g.manual_seed(seed)
+    tri = hits[:, 0]
+    hit = tri != -1
+    t = hits[hit, 1].view(torch.float32)
+    o, d = rays[hit, :3], rays[hit, 3:]
+    n = tri_n[tri[hit].long()]
+    n = torch.where((n * d).sum(1, keepdim=True) > 0, -n, n)
+    p = o + d * t[:, None] + n * (AO_OFFSET * ext)
+    p, n = p.repeat_interleave(AO_PER_HIT, 0), n.repeat_interleave(AO_PER_HIT, 0)
+    v = torch.randn(p.shape, generator=g, device=rays.device, dtype=torch.float32)
+    v = v / v.norm(dim=1, keepdim=True)
+    v = torch.where((v * n).sum(1, keepdim=True) < 0, -v, v)
+    return torch.cat([p, v], 1).contiguous()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scenes", type=int, nargs="+", default=[8, 1])
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--parent-lib", default=None, help="the parent commit's librt_tracer.so (file in the package directory)")
+    ap.add_argument("--ab-lib", action="append", default=[], help="NAME=LIB: the ray legs from another build too")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rays_bench.json"))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_rays.py measures on the GPU; none is visible")
+    mods = {"this": load("rtm_this", None)}
+    for spec in args.ab_lib:
+        name, lib = spec.split("=", 1)
+        mods[name] = load("rtm_" + name, lib)
+    parent = load("rtm_parent", args.parent_lib) if args.parent_lib else None
+    rtm = mods["this"]
+    res = {"tool": "tools/bench_rays.py", "frame": [W, H, SPP], "steps": args.steps, "warmup": args.warmup,
+           "samples": 5, "build_hash": rtm.library_build_hash(), "device": torch.cuda.get_device_name(0),
+           "arms": {k: m.library_build_hash() for k, m in mods.items()},
+           "parent_build_hash": parent.library_build_hash() if parent else None, "scenes": {}}
+    st = torch.cuda.current_stream().cuda_stream
+    n = W * H * SPP
+    for sid in args.scenes:
+        hs = {k: m.HostScene.load(sid) for k, m in mods.items()}
+        gs = {k: m.GpuScene(hs[k], 0) for k, m in mods.items()}
+        g0 = gs["this"]
+        f = g0.frame(W, H, SPP)
+        rays = g0.primary_rays(f)
+        torch.cuda.synchronize()
+        entry = {}
+
+        def ray_leg(r, sort=False):
+            fns = {k: (lambda g=g: g.trace_rays(r, stream=st)) for k, g in gs.items()}
+            ref = g0.trace_rays(r).hits
+            same = {k: bool(torch.equal(g.trace_rays(r).hits, ref)) for k, g in gs.items()}
+            if sort:            # (d): this build with RT_RAYS_SORT, the sort's own kernels inside the timed span
+                fns["this_sorted"] = lambda: g0.trace_rays(r, sort=True, stream=st)
+                same["this_sorted"] = bool(torch.equal(g0.trace_rays(r, sort=True).hits, ref))
+            out = measure(fns, r.shape[0], args.steps, args.warmup)
+            for k in out:
+                out[k]["unit"] = "rays/s"
+                out[k]["same_bits_as_this"] = same[k]
+            return {"rays": int(r.shape[0]), "hits": int((ref[:, 0] != -1).sum()), **out}
+
+        # (a) camera order, beside the frame
+        entry["a_camera_order"] = ray_leg(rays)
+        frames = {}
+        out = torch.empty(W * H, dtype=torch.int32, device="cuda")
+        fr = {"this": (rtm, g0, f)}
+        if parent:
+            ph = parent.HostScene.load(sid)
+            pg = parent.GpuScene(ph, 0)
+            fr["parent"] = (parent, pg, pg.frame(W, H, SPP))
+        fm = measure({k: (lambda g=g, ff=ff: g.render_frame_device(ff, out.data_ptr(), st)) for k, (_, g, ff) in fr.items()},
+                     n, args.steps, max(args.warmup, 40))
+        for k in fm:
+            fm[k]["unit"] = "samples/s"
+        entry["a_render_frame_device"] = fm
+        base = fm.get("parent", fm["this"])
+        entry["a_ratio_rays_over_frame"] = {"frame_from": "parent" if parent else "this",
+                                            "ratio": round(entry["a_camera_order"]["this"]["per_s"] / base["per_s"], 4)}
+        # (b) shuffled
+        perm = torch.from_numpy(np.random.Generator(np.random.PCG64(41)).permutation(n)).cuda()
+        shuffled = rays[perm].contiguous()
+        entry["b_shuffled"] = ray_leg(shuffled, sort=True)
+        # (c) one ambient-occlusion bounce
+        v, t = hs["this"].mesh()
+        tri_n = torch.from_numpy(np.ascontiguousarray(t[:, 3:6]).view(np.float32).copy()).cuda()
+        meta = hs["this"].grid()[0]
+        ext = float((meta["aabb_max"] - meta["aabb_min"]).max())
+        ao = ao_rays(rays, g0.trace_rays(rays).hits, tri_n, ext)
+        entry["c_ao_bounce"] = ray_leg(ao, sort=True)
+        # (d) the ordering pass against the unsorted call: it is kept only if it wins both legs by more than
+        # the larger of the two arms' spreads
+        d = {}
+        for leg in ("b_shuffled", "c_ao_bounce"):
+            u, so = entry[leg]["this"], entry[leg]["this_sorted"]
+            d[leg] = {"unsorted_ms": u["ms"], "sorted_ms": so["ms"], "speedup": round(u["ms"] / so["ms"], 3),
+                      "wins": bool(so["ms"] < u["ms"] * (1.0 - max(u["spread"], so["spread"])))}
+        d["also_camera_order"] = ray_leg(rays, sort=True)
+        entry["d_sort"] = d
+        res["scenes"][str(sid)] = entry
+        print(json.dumps({str(sid): entry}), flush=True)
+        for g in list(gs.values()) + ([pg] if parent else []):
+            g.close()
+        for h in list(hs.values()) + ([ph] if parent else []):
+            h.close()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()
