@@ -25,7 +25,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # Everything librt_tracer.so is compiled from: PMC counter files are valid only for this hash
 KERNEL_SOURCES = ("csrc/rt_kernels.hip", "csrc/rt_walk.h", "csrc/rt_kparams.h", "csrc/rt_plan.hip",
                   "csrc/rt_scene.h", "csrc/rt_tracer.hip", "csrc/rt_grid_build.hip", "csrc/rt_device.h",
-                  "csrc/rt_internal.h", "csrc/rt_box_words.h", "csrc/rt_fref_slots.h", "csrc/rt_record_gate.h", "csrc/rt_rays.hip", "csrc/Makefile",
+                  "csrc/rt_internal.h", "csrc/rt_box_words.h", "csrc/rt_fref_slots.h", "csrc/rt_record_gate.h", "csrc/rt_setup_div.h", "csrc/rt_rays.hip", "csrc/Makefile",
                   "../include/rt_tracer.h")
 
 
@@ -871,7 +871,7 @@ def unshard_device(width, height, nranks, d_gathered, d_out, stream=0):
            "rt_unshard_device")
 
 
-PRIM_WIDTHS = {0: (18, 8), 1: (12, 4), 2: (23, 6), 3: (3, 4), 4: (11, 3), 5: (18, 8), 6: (18, 8), 7: (12, 1)}
+PRIM_WIDTHS = {0: (18, 8), 1: (12, 4), 2: (23, 6), 3: (3, 4), 4: (11, 3), 5: (18, 8), 6: (18, 8), 7: (12, 1), 8: (2, 3)}
 
 
 def debug_rcp_check(device=0):

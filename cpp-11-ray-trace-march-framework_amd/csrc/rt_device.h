@@ -363,10 +363,10 @@ __device__ __forceinline__ bool point_in_aabb(float px, float py, float pz, cons
 }
 
 // aabb.h:34-83 (Williams et al.); IEEE inf/NaN from 1/+-0 select the slab order (H3, H9)
-__device__ __forceinline__ bool ray_aabb(float ox, float oy, float oz, float dx, float dy, float dz,
-                                         const float* mn, const float* mx, float& tmin, float& tmax)
+// (ray_aabb_rcp: with the caller's ix, iy, iz = 1.0f / d, which dda_setup also divides by)
+__device__ __forceinline__ bool ray_aabb_rcp(float ox, float oy, float oz, float ix, float iy, float iz,
+                                             const float* mn, const float* mx, float& tmin, float& tmax)
 {
-    const float ix = rcp_exact(dx), iy = rcp_exact(dy), iz = rcp_exact(dz);   // = 1.0f / d
     const bool sx = ix < 0.0f, sy = iy < 0.0f, sz = iz < 0.0f;
     tmin = ((sx ? mx[0] : mn[0]) - ox) * ix;
     tmax = ((sx ? mn[0] : mx[0]) - ox) * ix;
@@ -381,6 +381,12 @@ __device__ __forceinline__ bool ray_aabb(float ox, float oy, float oz, float dx,
     if (tzmin > tmin) tmin = tzmin;
     if (tzmax < tmax) tmax = tzmax;
     return true;
+}
+
+__device__ __forceinline__ bool ray_aabb(float ox, float oy, float oz, float dx, float dy, float dz,
+                                         const float* mn, const float* mx, float& tmin, float& tmax)
+{
+    return ray_aabb_rcp(ox, oy, oz, rcp_exact(dx), rcp_exact(dy), rcp_exact(dz), mn, mx, tmin, tmax);   // = 1.0f / d
 }
 
 // lin_alg.h:138-156 Dot (accumulates from T() = 0) and Normalize (1/sqrt, then scale; the

@@ -1122,6 +1122,16 @@ __global__ void __launch_bounds__(kWG) k_primitives(int kind, const float *in, u
         const float4 *a = reinterpret_cast<const float4 *>(in + 28 * size_t(i));
         out[i] = rtd::dist_point_tri(a[0].x, a[0].y, a[0].z, a[1], a[2], a[3], a[4], a[5], a[6]);
     }
+    else if (kind == 8)   // dda_setup's quotient (rt_setup_div.h) with its wave vote, beside the division
+    {
+        const float nn = in[2 * size_t(i)], d = in[2 * size_t(i) + 1];
+        const float r = rtd::rcp_nr(d);
+        const unsigned long long bad = setup_div_bad_lanes(nn) | setup_div_bad_lanes(d);
+        float *o = out + 3 * size_t(i);
+        o[0] = bad == 0ull ? setup_div(nn, d, r) : nn / d;
+        o[1] = nn / d;
+        o[2] = bad == 0ull ? 1.0f : 0.0f;     // 1: the wave took the reciprocal form
+    }
     else if (kind == 1)
     {
         const float *a = in + 12 * i;

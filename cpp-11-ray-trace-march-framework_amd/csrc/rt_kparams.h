@@ -114,6 +114,8 @@ struct KParams
     uint32_t tiles_x;           // 16x16 tiles across the region
     uint32_t rank, nranks;      // local tile k = row-rotated tile rank + k * nranks (shard_tile_xy)
     uint32_t wg_per_tile;
+    uint32_t ipt_shift;         // lane kernels: log2 of the work items per tile (wg_per_tile * kWavesPerWG = 4 spp)
+    uint32_t tiles_x_m;         // udiv_magic(tiles_x): the shard deal's t / tiles_x without a division
     uint32_t xcd_chunk;         // kVarXcdBands: consecutive blocks per XCD turn (0 = one band each)
     uint32_t vblocks;           // k_render_lanes_w64: the 256-lane launch blocks its one-wave grid runs
     uint64_t *wave_clk;        // kVarWaveClock: {start, end, uniform tests, lane-loop iterations} per item
@@ -251,6 +253,36 @@ __host__ __device__ __forceinline__ void shard_tile_xy(uint32_t k, uint32_t rank
     if (nranks > 1u)
     {
         const uint32_t r = (kShardRot * ty) % tiles_x;
+        tx = tx >= r ? tx - r : tx + tiles_x - r;
+    }
+}
+
+// t / d for any t < 2^32 and d >= 1 by one multiply-high and one correction: m = udiv_magic(d) =
+// floor(2^32 / d) (2^32 - 1 for d = 1) has 2^32 / d - 1 < m <= 2^32 / d, so t m / 2^32 lies in
+// (t / d - 1, t / d] and its floor is t / d or one less; the remainder test settles which.
+inline uint32_t udiv_magic(uint32_t d) { return d <= 1u ? 0xFFFFFFFFu : uint32_t(0x100000000ull / d); }
+__host__ __device__ __forceinline__ uint32_t udiv_by_magic(uint32_t t, uint32_t d, uint32_t m, uint32_t& rem)
+{
+    uint32_t q = uint32_t((uint64_t(t) * m) >> 32);
+    rem = t - q * d;
+    if (rem >= d)
+    {
+        q += 1u;
+        rem -= d;
+    }
+    return q;
+}
+
+// shard_tile_xy with the divisions by tiles_x as multiplications (tiles_x_m = udiv_magic(tiles_x)); the same
+// tx, ty for every k with rank + k * nranks < 2^32.
+__host__ __device__ __forceinline__ void shard_tile_xy_m(uint32_t k, uint32_t rank, uint32_t nranks, uint32_t tiles_x,
+                                                         uint32_t tiles_x_m, uint32_t& tx, uint32_t& ty)
+{
+    ty = udiv_by_magic(rank + k * nranks, tiles_x, tiles_x_m, tx);
+    if (nranks > 1u)
+    {
+        uint32_t r;
+        udiv_by_magic(kShardRot * ty, tiles_x, tiles_x_m, r);
         tx = tx >= r ? tx - r : tx + tiles_x - r;
     }
 }

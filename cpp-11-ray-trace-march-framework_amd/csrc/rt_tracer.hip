@@ -517,6 +517,8 @@ int launch_render(rt_scene *s, const rt_frame *f, KParams& P, uint32_t n_local_t
     const bool lanes = use_lanes(f, P.spp);
     P.wg_per_tile = lanes ? (kTilePix * P.spp) / kWG : 1;
     if (P.wg_per_tile == 0) P.wg_per_tile = 1;
+    P.ipt_shift = lanes ? log2u(P.wg_per_tile * kWavesPerWG) : 0u;     // (lanes: spp a power of two)
+    P.tiles_x_m = udiv_magic(P.tiles_x);
     const uint64_t blocks = uint64_t(n_local_tiles) * P.wg_per_tile;
     if (blocks > 0x3FFFFFFFull) return fail(RT_E_INVALID, "frame too large for one launch");
     const uint32_t kind = f->kernel & RT_KERNEL_KIND_MASK;
@@ -832,6 +834,8 @@ int launch_batch(rt_scene *const *S, const rt_frame *F, uint32_t n, KParams *P, 
     for (uint32_t i = 0; i < n; i++)
     {
         P[i].wg_per_tile = wgpt;
+        P[i].ipt_shift = log2u(wgpt * kWavesPerWG);
+        P[i].tiles_x_m = udiv_magic(P[i].tiles_x);
         P[i].xcd_chunk = ((P[i].tiles_x + P[i].nranks - 1u) / P[i].nranks) * wgpt;
     }
     // RT_KERNEL_FLAG_OVERLAP (every frame of the batch): this launch may run beside the scenes' last
@@ -2232,8 +2236,9 @@ int rt_debug_gamma_check(uint64_t *mismatches, int device)
 int rt_debug_primitives(int kind, const float *in, uint32_t n, float *out, int device)
 {
     // kind 7 (DistancePointTri) reaches the device as pos + pad + the 24-float scene record
-    static const uint32_t in_w[8] = { 18, 12, 23, 3, 11, 18, 18, 28 }, out_w[8] = { 8, 4, 6, 4, 3, 8, 8, 1 };
-    if (kind < 0 || kind > 7 || !in || !out) return fail(RT_E_INVALID, "bad arguments");
+    // kind 8: (n, d) -> {dda_setup's quotient, n / d, 1 when the wave took the reciprocal form} (rt_setup_div.h)
+    static const uint32_t in_w[9] = { 18, 12, 23, 3, 11, 18, 18, 28, 2 }, out_w[9] = { 8, 4, 6, 4, 3, 8, 8, 1, 3 };
+    if (kind < 0 || kind > 8 || !in || !out) return fail(RT_E_INVALID, "bad arguments");
     if (n == 0) return RT_OK;
     RT_HIP(hipSetDevice(device));
     std::vector<float> host_in;

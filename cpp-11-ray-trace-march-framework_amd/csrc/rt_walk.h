@@ -10,6 +10,7 @@
 #include "rt_device.h"
 #include "rt_kparams.h"
 #include "rt_record_gate.h"
+#include "rt_setup_div.h"
 
 namespace rtk {
 namespace {
@@ -625,18 +626,44 @@ __device__ __forceinline__ float box_exit_bound(float x, float dtv, int f)
 // grid.cpp:174-216), axis arrays unrolled into scalars.  Instead of pos/step/out per axis the
 // walk keeps the cells left before 'pos == out' (rem) and the signed GridIdx stride of a step
 // (cs): grid.cpp:274-277 exits after the same steps.  False when the ray misses the grid.
+// RCP_SETUP false: the division form -- ray_aabb's own reciprocals and six divisions -- for the one walk whose
+// kernel the reciprocal form costs a wave per SIMD (grid_intersect says which).
+#ifndef RT_SETUP_RCP            // (tools/build_variant.sh -DRT_SETUP_RCP=0: the A/B arm with the six divisions)
+#define RT_SETUP_RCP 1
+#endif
+template <bool RCP_SETUP = (RT_SETUP_RCP != 0)>
 __device__ __forceinline__ bool dda_setup(const KParams& P, float ox, float oy, float oz, float dx, float dy, float dz,
                                           float& nct0, float& nct1, float& nct2, float& dt0, float& dt1, float& dt2,
                                           int& rem0, int& rem1, int& rem2, int& cs0, int& cs1, int& cs2, int& cell,
                                           float *enter_out = nullptr)
 {
+    // One reciprocal per axis serves ray_aabb's slabs AND the six quotients below (rt_setup_div.h).
+    // ix = 1.0f / dx in every lane: rtd::rcp_nr where the whole wave's d lie in the quotients' window
+    // (inside rcp_nr's proven range), else -- a zero, tiny, huge or NaN component in some lane; rare --
+    // the wave divides, as rtd::rcp_exact does.  `bad`: lanes that fail the window so far (wave-uniform).
+    float ix = 0.0f, iy = 0.0f, iz = 0.0f;
+    unsigned long long bad = ~0ull;
+    if constexpr (RCP_SETUP)
+    {
+        ix = rtd::rcp_nr(dx);
+        iy = rtd::rcp_nr(dy);
+        iz = rtd::rcp_nr(dz);
+        bad = setup_div_bad_lanes(dx) | setup_div_bad_lanes(dy) | setup_div_bad_lanes(dz);
+        if (bad != 0ull)
+        {
+            ix = 1.0f / dx;
+            iy = 1.0f / dy;
+            iz = 1.0f / dz;
+        }
+    }
     float enter_t, leave_t, gx, gy, gz;
     if (rtd::point_in_aabb(ox, oy, oz, P.bmin, P.bmax))
     {
         enter_t = 0.0f;
         gx = ox; gy = oy; gz = oz;
     }
-    else if (rtd::ray_aabb(ox, oy, oz, dx, dy, dz, P.bmin, P.bmax, enter_t, leave_t))
+    else if (RCP_SETUP ? rtd::ray_aabb_rcp(ox, oy, oz, ix, iy, iz, P.bmin, P.bmax, enter_t, leave_t)
+                       : rtd::ray_aabb(ox, oy, oz, dx, dy, dz, P.bmin, P.bmax, enter_t, leave_t))
     {
         gx = ox + dx * enter_t;
         gy = oy + dy * enter_t;
@@ -654,27 +681,49 @@ __device__ __forceinline__ bool dda_setup(const KParams& P, float ox, float oy, 
     const int pos0 = to_voxel(gx, 0), pos1 = to_voxel(gy, 1), pos2 = to_voxel(gz, 2);
     dt0 = dt1 = dt2 = 0.0f;
     rem0 = rem1 = rem2 = cs0 = cs1 = cs2 = 0;
-    auto setup = [&](float d, float g, int pos, int a, int stride, float& nct, float& dtv, int& rem, int& cs) {
+    // The two numerators of an axis: the distance to the first cell face along d ((bmin + float(pos + 1) cw)
+    // - g for d > 0, (bmin + float(pos) cw) - g otherwise) and +-cw; both are divided by d.
+    auto face = [&](float d, float g, int pos, int a) { return (P.bmin[a] + float(d > 0.0f ? pos + 1 : pos) * P.cw) - g; };
+    const float n0 = face(dx, gx, pos0, 0), n1 = face(dy, gy, pos1, 1), n2 = face(dz, gz, pos2, 2);
+    const float c0 = dx > 0.0f ? P.cw : -P.cw, c1 = dy > 0.0f ? P.cw : -P.cw, c2 = dz > 0.0f ? P.cw : -P.cw;
+    // The six quotients: n / d's bits from the axis' reciprocal (setup_div, 5 instructions against the
+    // division's 11) when every lane's n and d and the cell width lie in its window, else by division.
+    const uint32_t cwb = __float_as_uint(P.cw) & 0x7FFFFFFFu;   // (positive floats order as their bits)
+    if constexpr (RCP_SETUP) bad |= setup_div_bad_lanes(n0) | setup_div_bad_lanes(n1) | setup_div_bad_lanes(n2);
+    float q0, q1, q2, w0, w1, w2;
+    if (RCP_SETUP && bad == 0ull && cwb >= __float_as_uint(kSetupDivLo) && cwb <= __float_as_uint(kSetupDivHi))
+    {
+        q0 = setup_div(n0, dx, ix); w0 = setup_div(c0, dx, ix);
+        q1 = setup_div(n1, dy, iy); w1 = setup_div(c1, dy, iy);
+        q2 = setup_div(n2, dz, iz); w2 = setup_div(c2, dz, iz);
+    }
+    else
+    {
+        q0 = n0 / dx; w0 = c0 / dx;
+        q1 = n1 / dy; w1 = c1 / dy;
+        q2 = n2 / dz; w2 = c2 / dz;
+    }
+    auto setup = [&](float d, float q, float w, int pos, int a, int stride, float& nct, float& dtv, int& rem, int& cs) {
         if (d == 0.0f)
             nct = rtd::kFltMax;
         else if (d > 0.0f)
         {
-            nct = enter_t + ((P.bmin[a] + float(pos + 1) * P.cw) - g) / d;
-            dtv = P.cw / d;
+            nct = enter_t + q;
+            dtv = w;
             rem = P.dim[a] - 1 - pos;           // steps until pos + 1 == dim
             cs = stride;
         }
         else
         {
-            nct = enter_t + ((P.bmin[a] + float(pos) * P.cw) - g) / d;
-            dtv = -P.cw / d;
+            nct = enter_t + q;
+            dtv = w;
             rem = pos;                          // steps until pos - 1 == -1
             cs = -stride;
         }
     };
-    setup(dx, gx, pos0, 0, 1, nct0, dt0, rem0, cs0);
-    setup(dy, gy, pos1, 1, P.dxdz, nct1, dt1, rem1, cs1);
-    setup(dz, gz, pos2, 2, P.dim[0], nct2, dt2, rem2, cs2);
+    setup(dx, q0, w0, pos0, 0, 1, nct0, dt0, rem0, cs0);
+    setup(dy, q1, w1, pos1, 1, P.dxdz, nct1, dt1, rem1, cs1);
+    setup(dz, q2, w2, pos2, 2, P.dim[0], nct2, dt2, rem2, cs2);
     cell = pos0 + pos2 * P.dim[0] + pos1 * P.dxdz;
     if (enter_out) *enter_out = enter_t;
     return true;
@@ -775,8 +824,15 @@ __device__ __forceinline__ bool grid_intersect(const KParams& P, float ox, float
 {
     float nct0, nct1, nct2, dt0, dt1, dt2;
     int rem0, rem1, rem2, cs0, cs1, cs2, cell;
-    if (!dda_setup(P, ox, oy, oz, dx, dy, dz, nct0, nct1, nct2, dt0, dt1, dt2, rem0, rem1, rem2, cs0, cs1, cs2,
-                   cell))
+    // (the ray-query walk with the Newton 1/det but without packed counts: its kernel stands at 63 VGPRs and
+    // went to 72 -- a wave per SIMD -- with the reciprocal form of the setup's quotients in this walk, its
+    // common one, so this instantiation keeps the divisions.  The same kernel's rare branch for long
+    // directions, rt_rays.hip's walk without kVarFastRcp, is another instantiation and takes the reciprocal
+    // form; both forms give n / d's bits)
+    constexpr bool RCP_SETUP = RT_SETUP_RCP != 0 &&
+                               ((VAR & kVarRays) == 0 || (VAR & kVarPackedRem) != 0 || (VAR & kVarFastRcp) == 0);
+    if (!dda_setup<RCP_SETUP>(P, ox, oy, oz, dx, dy, dz, nct0, nct1, nct2, dt0, dt1, dt2, rem0, rem1, rem2, cs0, cs1,
+                              cs2, cell))
         return false;
     t = rtd::kFltMax;
     uint32_t lpar = 0u;                 // kVarLdsSplit: the reduction buffers' parity (test_cell)
@@ -1297,14 +1353,67 @@ __device__ __forceinline__ ItemCoord tile_slot_coord(const KParams& P, uint32_t 
     return ic;
 }
 
-// Pixel/sample of this lane in work item `item` (wave-uniform).  Called before AND after the
-// traversal so none of it is live (in VGPRs) across the DDA walk.
+// Pixel/sample of this lane in work item `item` (wave-uniform): the compact kernel's and the wide
+// section's form, for any tile size (process_item has its own, item_coord_pre / item_coord_post).
 __device__ __forceinline__ ItemCoord item_coord(const KParams& P, uint32_t item, uint32_t lane)
 {
     const uint32_t items_per_tile = P.wg_per_tile * kWavesPerWG;
     const uint32_t kseq = item / items_per_tile;              // position in the launch's tile order
     const uint32_t slot = (item - kseq * items_per_tile) * 64u + lane;
     return tile_slot_coord(P, P.tile_order ? P.tile_order[kseq] : kseq, slot);   // local tile k
+}
+
+// process_item's form of item_coord.  Before the walk (item_coord_pre): the same coordinates with the
+// two u32 divisions replaced -- the work items per tile are a power of two in every lane kernel
+// (P.ipt_shift), and the shard deal divides by P.tiles_x through its magic (shard_tile_xy_m).  The
+// item's TILE ORIGIN then crosses the walk in ONE packed VGPR (tile_origin_word: tx0 | ty0 << 16 --
+// every launched tile holds a pixel of the region, so tx0 < rx0 + rw <= 65536 and ty0 likewise:
+// validate_frame; wave-uniform, but kept in a VGPR: the kernel has no SGPR to spare across the walk),
+// and item_coord_post rebuilds the whole ItemCoord from it in full 32-bit arithmetic, so a lane of a
+// tile that overhangs the region (x or y up to 15 past it, past 2^16 too) is invalid exactly as
+// item_coord finds it: the Morton offsets come from the lane, the sample is the lane's low bits,
+// validity the same two compares.
+__device__ __forceinline__ ItemCoord item_coord_pre(const KParams& P, uint32_t item, uint32_t lane)
+{
+    const uint32_t kseq = item >> P.ipt_shift;                // position in the launch's tile order
+    const uint32_t slot = ((item - (kseq << P.ipt_shift)) << 6) + lane;
+    ItemCoord ic;
+    ic.c.k = P.tile_order ? P.tile_order[kseq] : kseq;        // local tile k
+    uint32_t tx, ty;
+    shard_tile_xy_m(ic.c.k, P.rank, P.nranks, P.tiles_x, P.tiles_x_m, tx, ty);
+    ic.c.tx0 = P.rx0 + tx * kTile;
+    ic.c.ty0 = P.ry0 + ty * kTile;
+    ic.p = slot >> P.spp_shift;
+    ic.s = slot & (P.spp - 1u);
+    ic.x = ic.c.tx0 + compact_bits(ic.p);
+    ic.y = ic.c.ty0 + compact_bits(ic.p >> 1);
+    ic.valid = ic.x < P.rx0 + P.rw && ic.y < P.ry0 + P.rh;
+    return ic;
+}
+
+// The tile origin of an ItemCoord as one word held in a VGPR (the empty asm keeps the compiler from
+// carrying the wave-uniform value in an SGPR across the walk).
+__device__ __forceinline__ uint32_t tile_origin_word(const ItemCoord& ic)
+{
+    uint32_t w = ic.c.tx0 | (ic.c.ty0 << 16);
+    asm volatile("" : "+v"(w));
+    return w;
+}
+
+__device__ __forceinline__ ItemCoord item_coord_post(const KParams& Q, uint32_t item, uint32_t lane, uint32_t origin)
+{
+    const uint32_t kseq = item >> Q.ipt_shift;
+    const uint32_t o = __builtin_amdgcn_readfirstlane(origin);
+    ItemCoord ic;
+    ic.c.k = Q.tile_order ? Q.tile_order[kseq] : kseq;
+    ic.c.tx0 = o & 0xFFFFu;
+    ic.c.ty0 = o >> 16;
+    ic.p = (((item - (kseq << Q.ipt_shift)) << 6) + lane) >> Q.spp_shift;
+    ic.s = lane & (Q.spp - 1u);
+    ic.x = ic.c.tx0 + compact_bits(ic.p);
+    ic.y = ic.c.ty0 + compact_bits(ic.p >> 1);
+    ic.valid = ic.x < Q.rx0 + Q.rw && ic.y < Q.ry0 + Q.rh;
+    return ic;
 }
 
 // The record of one sample of AUTO's walk (rt_render_records_device), raw (store_record): a box-run
@@ -1331,13 +1440,15 @@ __device__ __forceinline__ void process_item(const KParams& P, uint32_t item, ui
     float cr = 0.0f, cg = 0.0f, cb = 0.0f;
     uint32_t hit_tri = rtd::kNoTri;
     SampleOut so{false, 0.0f, 0.0f, 0.0f, rtd::kNoTri, rtd::kNoTri};
+    uint32_t origin;
     {
-        const ItemCoord ic = item_coord(P, item, lane);
+        const ItemCoord ic = item_coord_pre(P, item, lane);
+        origin = tile_origin_word(ic);
         if (ic.valid)
             trace_sample<false, TRI, VAR>(P, ic.x, ic.y, ic.s, cr, cg, cb, hit_tri, nullptr, off, &so);
     }
     const KParams& Q = late_params(P, off);
-    const ItemCoord ic = item_coord(Q, item, lane);
+    const ItemCoord ic = item_coord_post(Q, item, lane, origin);
     // kVarLdsSplit: the workgroup's four waves traced the same samples; wave 0 stores them
     const bool owner = (VAR & kVarLdsSplit) == 0 || threadIdx.x < 64u;
     // rt_render_hits_device only: the sample's hit triangle, after the walk (a scalar test of a

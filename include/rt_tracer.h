@@ -350,7 +350,8 @@ int  rt_trace_samples(rt_scene *scene, const rt_frame *frame, uint32_t x0, uint3
  * 5 the branch-free ray/tri forms the traversal uses (18 in, 8 out; t,u,v valid on hits),
  * 6 the wave-gated forms: pre-gated MT, gated MT (18 in, 8 out; t,u,v valid on hits),
  * 7 DistancePointTri through the ray-march kernel's per-triangle record (12 in: pos, v0, v1,
- * v2; 1 out). */
+ * v2; 1 out), 8 the DDA setup's quotient (2 in: n, d; 3 out: the quotient as the walk's setup
+ * forms it, wave vote included, the IEEE n / d, 1.0 when the record's wave took the reciprocal form). */
 int  rt_debug_primitives(int kind, const float *in, uint32_t n, float *out, int device);
 /* Exhaustive check of the kernels' Newton-refined reciprocal (rt_device.h rcp_nr) against the
    correctly rounded 1.0f / x for all 2^32 - 2^24 finite nonzero floats; bad_by_exponent[256]
