@@ -25,7 +25,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # Everything librt_tracer.so is compiled from: PMC counter files are valid only for this hash
 KERNEL_SOURCES = ("csrc/rt_kernels.hip", "csrc/rt_walk.h", "csrc/rt_kparams.h", "csrc/rt_plan.hip",
                   "csrc/rt_scene.h", "csrc/rt_tracer.hip", "csrc/rt_grid_build.hip", "csrc/rt_device.h",
-                  "csrc/rt_internal.h", "csrc/rt_box_words.h", "csrc/rt_fref_slots.h", "csrc/rt_record_gate.h", "csrc/rt_setup_div.h", "csrc/rt_rays.hip", "csrc/Makefile",
+                  "csrc/rt_internal.h", "csrc/rt_box_words.h", "csrc/rt_fref_slots.h", "csrc/rt_record_gate.h", "csrc/rt_setup_div.h", "csrc/rt_rays.hip",
+                  "csrc/rt_ray_common.h", "csrc/rt_occlusion.hip", "csrc/Makefile",
                   "../include/rt_tracer.h")
 
 
@@ -67,7 +68,7 @@ TRACER_SYMBOLS = [
     "rt_scene_create_from_mesh", "rt_kernel_times", "rt_render_frame_host", "rt_frame_host_wait", "rt_host_alloc",
     "rt_host_free", "rt_render_hits_device", "rt_scene_info_get", "rt_build_hash", "rt_render_batch_device",
     "rt_render_records_device", "rt_render_frame_host_tiled", "rt_fref_buffer_bytes",
-    "rt_trace_rays_device", "rt_primary_rays_device",
+    "rt_trace_rays_device", "rt_primary_rays_device", "rt_occluded_rays_device",
 ]
 MAX_BATCH = 10                           # frames per rt_render_batch_device launch (kMaxBatch)
 
@@ -206,6 +207,8 @@ def tracer_lib():
         if hasattr(L, "rt_trace_rays_device"):       # absent in earlier builds (A/B runs)
             L.rt_trace_rays_device.argtypes = [vp, vp, c_u32, c_u32, vp, vp, vp]
             L.rt_primary_rays_device.argtypes = [vp, ctypes.POINTER(Frame), vp, vp]
+        if hasattr(L, "rt_occluded_rays_device"):    # absent in earlier builds (A/B runs)
+            L.rt_occluded_rays_device.argtypes = [vp, vp, vp, c_u32, c_u32, vp, vp]
         L.rt_unshard_device.argtypes = [c_u32, c_u32, c_u32, vp, vp, vp]
         L.rt_last_kernel_ms.argtypes = [vp, ctypes.POINTER(c_f32)]
         L.rt_trace_samples.argtypes = [vp, ctypes.POINTER(Frame), c_u32, c_u32, c_u32, c_u32, vp]
@@ -753,6 +756,58 @@ class GpuScene:
         tri = hits[:, 0].view(u32) if u32 is not None else hits[:, 0]
         return RayHits(tri, hits[:, 1].view(torch.float32), hits[:, 2].view(torch.float32),
                        hits[:, 3].view(torch.float32), hits, rec)
+
+    def occluded(self, rays, tminmax=None, sort=False, stream=None):
+        """rt_occluded_rays_device: is anything hit inside the open interval (tmin, tmax) of each ray?  The
+        any-hit walk of include/rt_tracer.h: Grid::Intersect ended by the first test that counts, and by the
+        first step whose crossing time is >= tmax; t is in units of the direction as passed.
+
+        rays [n, 6] and tminmax [n, 2] (None: (-inf, +inf) for every ray): contiguous float32 torch CUDA tensors
+        on the scene's device, used in place through data_ptr(), asynchronously on `stream` as trace_rays does
+        -> a torch.uint8 [n] tensor of 1 / 0; or C-contiguous float32 numpy arrays, which are uploaded ->
+        a numpy bool [n] (synchronous).  The two inputs are of one kind.  Anything else raises ValueError before
+        any launch.  sort=True (RT_RAYS_SORT): the same bytes, the rays traced in sorted order."""
+        import torch
+        host = isinstance(rays, np.ndarray)
+        if host:
+            if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != RAY_WORDS or not rays.flags["C_CONTIGUOUS"]:
+                raise ValueError("rays: a C-contiguous float32 array of shape [n, 6]")
+            n = rays.shape[0]
+            if tminmax is not None and (not isinstance(tminmax, np.ndarray) or tminmax.dtype != np.float32 or
+                                        tminmax.shape != (n, 2) or not tminmax.flags["C_CONTIGUOUS"]):
+                raise ValueError("tminmax: a C-contiguous float32 array of shape [n, 2], as the rays")
+            dev = torch.device(f"cuda:{self.device}")
+            d_rays = torch.from_numpy(rays).to(dev)
+            d_tmm = torch.from_numpy(tminmax).to(dev) if tminmax is not None else None
+        elif isinstance(rays, torch.Tensor):
+            if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != RAY_WORDS:
+                raise ValueError("rays: a float32 tensor of shape [n, 6]")
+            if not rays.is_cuda or rays.device.index != self.device:
+                raise ValueError(f"rays: a tensor on cuda:{self.device} (host memory is not traced in place)")
+            if not rays.is_contiguous():
+                raise ValueError("rays: a contiguous tensor (a strided view would be read as other rays)")
+            n = rays.shape[0]
+            if tminmax is not None:
+                if not isinstance(tminmax, torch.Tensor) or tminmax.dtype != torch.float32 or tuple(tminmax.shape) != (n, 2):
+                    raise ValueError("tminmax: a float32 tensor of shape [n, 2], as the rays")
+                if tminmax.device != rays.device or not tminmax.is_contiguous():
+                    raise ValueError("tminmax: a contiguous tensor on the rays' device")
+            d_rays, d_tmm, dev = rays, tminmax, rays.device
+        else:
+            raise ValueError("rays: a torch CUDA tensor or a numpy array")
+        occ = torch.empty((n,), dtype=torch.uint8, device=dev)
+        if stream is not None and int(stream) != torch.cuda.current_stream(dev).cuda_stream:
+            occ.record_stream(torch.cuda.ExternalStream(int(stream), device=dev))     # (as trace_rays)
+        L = tracer_lib()
+        _check(L.rt_occluded_rays_device(self._h, ctypes.c_void_p(d_rays.data_ptr()),
+                                         ctypes.c_void_p(d_tmm.data_ptr() if d_tmm is not None and n else 0), n,
+                                         RT_RAYS_SORT if sort else 0, ctypes.c_void_p(occ.data_ptr()),
+                                         ctypes.c_void_p(self._stream(torch, stream))), L, "rt_occluded_rays_device")
+        if host:
+            if stream is not None:
+                torch.cuda.synchronize(dev)            # the copy below runs on torch's stream
+            return occ.cpu().numpy().astype(bool)
+        return occ
 
     def close(self):
         if getattr(self, "_h", None):

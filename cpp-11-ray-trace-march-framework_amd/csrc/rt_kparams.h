@@ -52,6 +52,9 @@ constexpr int kVarLdsSplit = 4194304;       // the wide section's LDS tier: the 
 constexpr int kVarRays = 8388608;           // rt_trace_rays_device (rt_rays.hip): caller-supplied rays, one per
                                             // lane and unrelated to their neighbours -- the box-run walk stays in
                                             // its per-lane phase and the record test reads the 48-byte refs
+constexpr int kVarAnyHit = 16777216;        // rt_occluded_rays_device (rt_occlusion.hip), only with kVarRays: the walk
+                                            // ends at the first test that counts inside (tmin, tmax) and at the first
+                                            // step whose crossing is >= tmax (grid_intersect); no t, u, v, tri
 // AUTO's traversal: every feature above that is exact for every scene ...
 constexpr int kVarAutoCore = kVarWaveGate | kVarDistSkip | kVarOriginPre | kVarXcdBands | kVarUniform;
 // ... plus the two that need a scene property (rt_scene::rcp_safe, rt_scene::pack_ok)
@@ -322,5 +325,9 @@ rays_fn trace_rays_kernel(int var, bool count);
 primary_fn primary_rays_kernel();
 ray_keys_fn ray_keys_kernel();                  // k_ray_keys(P, rays, n, shift, keys): RT_RAYS_SORT's sort words
 uint32_t ray_key_bits();                        // ... which are sorted by this many low bits
+// rt_occlusion.hip: k_occluded_rays<var>(P, rays, tminmax, order, n, occluded) -- var: k_trace_rays' fast-arm variant |
+// kVarAnyHit; tminmax null: (-inf, +inf) for every ray
+using occluded_fn = void (*)(KParams, const float2 *, const float2 *, const unsigned long long *, uint32_t, uint8_t *);
+occluded_fn occluded_rays_kernel(int var);
 
 } // namespace rtk

@@ -1,0 +1,31 @@
+// rt_ray_common.h -- what the ray-query translation units share (rt_rays.hip: rt_trace_rays_device;
+// rt_occlusion.hip: rt_occluded_rays_device) beside rt_walk.h's walk.
+#pragma once
+#include "rt_walk.h"
+
+namespace rtk {
+namespace {
+
+// One class test per component: anything but NaN and +-inf (v_cmp_class_f32; mask bits 3-8: the
+// normal, subnormal and zero classes of either sign).
+__device__ __forceinline__ bool finite_f32(float x)
+{
+    return __builtin_amdgcn_classf(x, 0x1F8);
+}
+
+// kVarFastRcp for rays: rt_scene::rcp_safe bounds |e1|_1 |e2|_1 below 2^120, which keeps
+// |det| = |e1 . (d x e2)| <= 2 |d|_inf |e1|_1 |e2|_1 inside rcp_nr's exact range (< 2^126) for a
+// direction of |d|_inf <= kRcpMaxDir with a factor of 4 to spare for the roundings; the camera's unit
+// directions are far inside.  d is used as the caller passes it, so a wave that holds a longer direction
+// takes the same walk with the correctly rounded division instead (a wave-uniform choice: same bits).
+constexpr float kRcpMaxDir = 8.0f;
+
+// RT_RAYS_SORT: a ray's sort word is index << kKeyBits | key (rt_rays.hip, k_ray_keys)
+constexpr uint32_t kKeyBits = 32;
+
+// the ray kernels' variants: kRaysBase [| kVarFastRcp] [| kRaysBox] (rt_tracer.hip scene_traversal_bits)
+constexpr int kRaysBase = kVarRays | kVarWaveGate | kVarDistSkip;
+constexpr int kRaysBox = kVarPackedRem | kVarSkipRun;
+
+} // namespace
+} // namespace rtk

@@ -18,24 +18,10 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "rt_walk.h"
+#include "rt_ray_common.h"     // finite_f32, kRcpMaxDir, kKeyBits, kRaysBase / kRaysBox: shared with rt_occlusion.hip
 
 namespace rtk {
 namespace {
-
-// One class test per component: anything but NaN and +-inf (v_cmp_class_f32; mask bits 3-8: the
-// normal, subnormal and zero classes of either sign).
-__device__ __forceinline__ bool finite_f32(float x)
-{
-    return __builtin_amdgcn_classf(x, 0x1F8);
-}
-
-// kVarFastRcp for rays: rt_scene::rcp_safe bounds |e1|_1 |e2|_1 below 2^120, which keeps
-// |det| = |e1 . (d x e2)| <= 2 |d|_inf |e1|_1 |e2|_1 inside rcp_nr's exact range (< 2^126) for a
-// direction of |d|_inf <= kRcpMaxDir with a factor of 4 to spare for the roundings; the camera's unit
-// directions are far inside.  d is used as the caller passes it, so a wave that holds a longer direction
-// takes the same walk with the correctly rounded division instead (a wave-uniform choice: same bits).
-constexpr float kRcpMaxDir = 8.0f;
 
 // RT_RAYS_SORT: a ray's sort word is index << kKeyBits | key, sorted by its low kKeyBits bits (stable: equal
 // keys keep input order).  key = direction octant << 27 | Morton code of the clamped entry cell (9 bits an
@@ -43,7 +29,6 @@ constexpr float kRcpMaxDir = 8.0f;
 // the largest key (kMissKey: above every octant's).  Any key is a valid one: the order only decides which
 // rays share a wave.  The key field is 32 bits -- four WHOLE 8-bit digits of the radix sort, which reads
 // whole digits: no bit of the index is ever part of a digit -- and the index (n < 2^31) sits above it.
-constexpr uint32_t kKeyBits = 32;
 constexpr uint32_t kMissKey = 0x7FFFFFFFu;
 
 __device__ __forceinline__ uint32_t spread3(uint32_t v)      // 9 bits -> every third bit
@@ -166,9 +151,6 @@ __global__ void __launch_bounds__(kWG) k_primary_rays(KParams P, float2 *rays, u
     rp[1] = make_float2(P.org[2], dx);
     rp[2] = make_float2(dy, dz);
 }
-
-constexpr int kRaysBase = kVarRays | kVarWaveGate | kVarDistSkip;
-constexpr int kRaysBox = kVarPackedRem | kVarSkipRun;
 
 } // namespace
 

@@ -2029,6 +2029,34 @@ int rt_trace_samples(rt_scene *s, const rt_frame *f, uint32_t x0, uint32_t y0, u
     return RT_OK;
 }
 
+// RT_RAYS_SORT, under the scene's mutex: sort words (k_ray_keys) -> the grid build's radix sort; *sorted is the
+// order the ray kernel then reads its rays through.  The scratch is the scene's and is the one piece of state
+// the ray queries have: sorted calls are serialised by the scene's mutex, and one on another stream than the
+// last waits for it (rays_ev).  It grows -- a free and an allocation, which wait for the device -- only when
+// n exceeds every earlier sorted n.  rays_sorted_done, after the kernel's launch, marks the scratch's last use.
+static int rays_sorted_order(rt_scene *s, const KParams& P, const float2 *rays, uint32_t n, hipStream_t st,
+                             unsigned long long **sorted)
+{
+    if (!s->rays_ev) RT_HIP(hipEventCreateWithFlags(&s->rays_ev, s->ev_order_flags));
+    if (s->rays_ev_recorded && st != s->rays_stream) RT_HIP(hipStreamWaitEvent(st, s->rays_ev, 0));
+    unsigned long long *keys = nullptr;
+    if (int rc = rt_internal_sort_reserve(&s->rays_sort, n, &keys)) return rc;
+    // cells per axis beyond 512 drop their low bits from the key (9 bits an axis)
+    uint32_t shift = 0;
+    while ((std::max(std::max(s->dims[0], s->dims[1]), s->dims[2]) - 1u) >> shift >= 512u) shift++;
+    hipLaunchKernelGGL(ray_keys_kernel(), dim3((n + kWG - 1) / kWG), dim3(kWG), 0, st, P, rays, n, shift, keys);
+    RT_HIP(hipGetLastError());
+    return rt_internal_sort_run(s->rays_sort, st, n, ray_key_bits(), sorted);
+}
+
+static int rays_sorted_done(rt_scene *s, hipStream_t st)
+{
+    RT_HIP(hipEventRecord(s->rays_ev, st));
+    s->rays_stream = st;
+    s->rays_ev_recorded = true;
+    return RT_OK;
+}
+
 // Every argument is checked before the scene is touched.  Without RT_RAYS_SORT no lock and no events: the
 // launch reads only what rt_scene_create wrote (scene_params), so it is ordered against nothing but its
 // own stream.
@@ -2067,28 +2095,57 @@ int rt_trace_rays_device(rt_scene *s, const rt_ray *d_rays, uint32_t n, uint32_t
         RT_HIP(hipGetLastError());
         return RT_OK;
     }
-    // RT_RAYS_SORT: sort words (k_ray_keys) -> the grid build's radix sort -> the same trace kernel reading
-    // its rays through the sorted words.  The scratch is the scene's and is the one piece of state this
-    // path has: sorted calls are serialised by the scene's mutex, and one on another stream than the last
-    // waits for it (rays_ev).  It grows -- a free and an allocation, which wait for the device -- only when
-    // n exceeds every earlier sorted n.
+    // RT_RAYS_SORT: the same trace kernel reading its rays through the sorted words (rays_sorted_order)
     std::lock_guard<std::mutex> lk(s->mtx);
-    if (!s->rays_ev) RT_HIP(hipEventCreateWithFlags(&s->rays_ev, s->ev_order_flags));
-    if (s->rays_ev_recorded && st != s->rays_stream) RT_HIP(hipStreamWaitEvent(st, s->rays_ev, 0));
-    unsigned long long *keys = nullptr, *sorted = nullptr;
-    if (int rc = rt_internal_sort_reserve(&s->rays_sort, n, &keys)) return rc;
-    // cells per axis beyond 512 drop their low bits from the key (9 bits an axis)
-    uint32_t shift = 0;
-    while ((std::max(std::max(s->dims[0], s->dims[1]), s->dims[2]) - 1u) >> shift >= 512u) shift++;
-    hipLaunchKernelGGL(ray_keys_kernel(), grid, wg, 0, st, P, rays, n, shift, keys);
-    RT_HIP(hipGetLastError());
-    if (int rc = rt_internal_sort_run(s->rays_sort, st, n, ray_key_bits(), &sorted)) return rc;
+    unsigned long long *sorted = nullptr;
+    if (int rc = rays_sorted_order(s, P, rays, n, st, &sorted)) return rc;
     hipLaunchKernelGGL(fn, grid, wg, 0, st, P, rays, static_cast<const unsigned long long *>(sorted), n, d_hits, d_recs);
     RT_HIP(hipGetLastError());
-    RT_HIP(hipEventRecord(s->rays_ev, st));
-    s->rays_stream = st;
-    s->rays_ev_recorded = true;
-    return RT_OK;
+    return rays_sorted_done(s, st);
+}
+
+// Ray i is occluded iff the any-hit walk over (tmin, tmax) finds a test that counts (include/rt_tracer.h).  The
+// argument rules, the variant table, the sort path and the absence of state without RT_RAYS_SORT are
+// rt_trace_rays_device's.
+int rt_occluded_rays_device(rt_scene *s, const rt_ray *d_rays, const float *d_tminmax, uint32_t n, uint32_t flags,
+                            uint8_t *d_occluded, void *hip_stream)
+{
+    if (!s) return fail(RT_E_INVALID, "scene is NULL");
+    if (flags & RT_RAYS_COUNT) return fail(RT_E_INVALID, "RT_RAYS_COUNT: the occlusion walk has no counting arm");
+    if (flags & ~uint32_t(RT_RAYS_SORT)) return fail(RT_E_INVALID, "unknown rt_rays_flags bit");
+    const bool sort = (flags & RT_RAYS_SORT) != 0u;
+    if (n >= 0x80000000u) return fail(RT_E_INVALID, "n must be below 2^31");
+    if (n == 0) return RT_OK;
+    if (!d_rays) return fail(RT_E_INVALID, "d_rays is NULL");
+    if (!d_occluded) return fail(RT_E_INVALID, "d_occluded is NULL");
+    if ((uintptr_t(d_rays) | uintptr_t(d_tminmax)) & 7u)
+        return fail(RT_E_INVALID, "d_rays and d_tminmax must be 8-byte aligned");
+    if (int rc = ensure_device(s)) return rc;
+    KParams P;
+    std::memset(&P, 0, sizeof(P));
+    scene_params(s, P);
+    P.frefs = nullptr;                  // per-camera-origin state: not this path's
+    P.gates = nullptr;
+    const int var = kVarAnyHit | kVarRays | kVarWaveGate | kVarDistSkip | scene_traversal_bits(s);
+    const occluded_fn fn = occluded_rays_kernel(var);
+    if (!fn) return fail(RT_E_INVALID, "kernel variant not built: " + std::to_string(var));
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const float2 *rays = reinterpret_cast<const float2 *>(d_rays);
+    const float2 *tmm = reinterpret_cast<const float2 *>(d_tminmax);
+    const dim3 grid((n + kWG - 1) / kWG), wg(kWG);
+    if (!sort)
+    {
+        hipLaunchKernelGGL(fn, grid, wg, 0, st, P, rays, tmm, static_cast<const unsigned long long *>(nullptr), n,
+                           d_occluded);
+        RT_HIP(hipGetLastError());
+        return RT_OK;
+    }
+    std::lock_guard<std::mutex> lk(s->mtx);
+    unsigned long long *sorted = nullptr;
+    if (int rc = rays_sorted_order(s, P, rays, n, st, &sorted)) return rc;
+    hipLaunchKernelGGL(fn, grid, wg, 0, st, P, rays, tmm, static_cast<const unsigned long long *>(sorted), n, d_occluded);
+    RT_HIP(hipGetLastError());
+    return rays_sorted_done(s, st);
 }
 
 int rt_primary_rays_device(rt_scene *s, const rt_frame *f, rt_ray *d_rays, void *hip_stream)

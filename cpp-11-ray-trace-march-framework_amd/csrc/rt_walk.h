@@ -215,12 +215,19 @@ __device__ __forceinline__ void lane_list(const KParams& P, rtd::f2v ra, rtd::f2
 template <bool STATS, int TRI, int VAR>
 __device__ __forceinline__ bool test_cell(const KParams& P, float ox, float oy, float oz, float dx, float dy,
                                           float dz, uint32_t kb, uint32_t ke, float nct_ax, float& t,
-                                          float& u, float& v, uint32_t& tri, uint32_t& tests, uint32_t& lpar)
+                                          float& u, float& v, uint32_t& tri, uint32_t& tests, uint32_t& lpar,
+                                          float tmin = 0.0f)
 {
     constexpr bool PRE = (VAR & kVarOriginPre) != 0 && TRI == RT_TRI_MOLLER_TRUMBORE;
     constexpr bool F = (VAR & kVarFastRcp) != 0;
     constexpr bool SPLIT = (VAR & kVarLdsSplit) != 0;
+    // kVarAnyHit (rt_occluded_rays_device): t holds the ray's tmax and is never lowered, so tb below is
+    // min(tmax, nct_ax); a test counts when it also lies above tmin, and the first one that counts ends the
+    // lane's list (true).  u, v, tri are not written.
+    constexpr bool ANY = (VAR & kVarAnyHit) != 0;
     static_assert(!SPLIT || (PRE && !STATS), "the LDS tier runs AUTO's record test");
+    static_assert(!ANY || ((VAR & kVarRays) != 0 && (VAR & kVarWaveGate) != 0 && !PRE && !STATS &&
+                           TRI == RT_TRI_MOLLER_TRUMBORE), "the any-hit walk is the ray queries' fast arm");
     (void)lpar;
     // wave-uniform, and the same in every wave of the workgroup (their lanes and lists are the same)
     bool split = false;
@@ -447,6 +454,28 @@ __device__ __forceinline__ bool test_cell(const KParams& P, float ox, float oy, 
     {
         if (!uniform_done) lane_list<STATS, VAR>(P, ra, rc, kb, ke, tb, u, v, tri, tests, first, step);
     }
+    else if constexpr (ANY)
+    {
+        // The list in order, as below, until this lane's first test that counts: hit, cur_t < nct_ax,
+        // tmin < cur_t and cur_t < tmax, all strict (tb = min(tmax, nct_ax): neither is NaN here -- the kernel
+        // walks no ray whose bounds are -- and a NaN nct_ax makes tb NaN, which counts nothing, as the
+        // reference's own compare against it).  A lane that found one leaves the loop; the others go on, and
+        // the det / u vote inside the test is exact for whichever lanes still take part.
+        // (the lane leaves through the loop's own bound, so the loop keeps its single exit: a second one in the
+        // middle is carried as a lane mask)
+        bool counted = false;
+        for (uint32_t k = kb; k < ke; k++)
+        {
+            const float4 *rp = P.refs + size_t(k) * 3;
+            const float4 r0 = rp[0], r1 = rp[1], r2 = rp[2];
+            float ct = 0.0f, cu, cv;
+            const bool hit = rtd::ray_tri_mt_gated<F>(ox, oy, oz, dx, dy, dz, r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z,
+                                                      r1.w, r2.x, ct, cu, cv);
+            counted = hit & (ct < tb) & (tmin < ct);
+            ke = counted ? 0u : ke;
+        }
+        return counted;
+    }
     else
     for (uint32_t k = kb; k < ke; k++)
     {
@@ -604,6 +633,19 @@ constexpr int kRemGuards = int((1u << 10) | (1u << 21) | (1u << 31));
         const float m_ = __builtin_fminf(__builtin_fminf(nct0, nct1), nct2);                   \
         const bool a2_ = nct2 == m_;                                                           \
         const bool e1_ = nct1 == m_;                                                           \
+        boxw -= a2_ ? (1 << 22) : (e1_ ? (1 << 11) : 1);                                       \
+        nct0 += (a2_ | e1_) ? 0.0f : dt0;                                                      \
+        nct1 += (e1_ & !a2_) ? dt1 : 0.0f;                                                     \
+        nct2 += a2_ ? dt2 : 0.0f;                                                              \
+    } while (0)
+// RT_DDA_BOX_BARE_STEP that also hands out the crossing it takes (kVarAnyHit: the last one of a run is the
+// run's largest, which decides whether the walk has passed tmax).
+#define RT_DDA_BOX_BARE_STEP_T(NCT_AX)                                                         \
+    do {                                                                                       \
+        const float m_ = __builtin_fminf(__builtin_fminf(nct0, nct1), nct2);                   \
+        const bool a2_ = nct2 == m_;                                                           \
+        const bool e1_ = nct1 == m_;                                                           \
+        NCT_AX = m_;                                                                           \
         boxw -= a2_ ? (1 << 22) : (e1_ ? (1 << 11) : 1);                                       \
         nct0 += (a2_ | e1_) ? 0.0f : dt0;                                                      \
         nct1 += (e1_ & !a2_) ? dt1 : 0.0f;                                                     \
@@ -820,8 +862,19 @@ template <bool STATS, int TRI, int VAR>
 __device__ __forceinline__ bool grid_intersect(const KParams& P, float ox, float oy, float oz,
                                                float dx, float dy, float dz,
                                                float& t, float& u, float& v, uint32_t& tri,
-                                               uint32_t& voxel, uint32_t& steps, uint32_t& tests)
+                                               uint32_t& voxel, uint32_t& steps, uint32_t& tests, float tmin = 0.0f)
 {
+    // kVarAnyHit (rt_occluded_rays_device, include/rt_tracer.h): the same walk over (tmin, tmax), tmax passed
+    // in t.  It returns true at the first test that counts (test_cell) and false at the first step whose
+    // crossing time is >= tmax (`stop` below: one compare per step on the crossing the advance hands out; a NaN
+    // crossing stops nothing).  Both exits only end the walk sooner, and nothing is indexed by tmin or tmax:
+    // the arguments on termination and on `cell` below hold unchanged.  t, u, v, tri, voxel are not written.
+    constexpr bool ANY = (VAR & kVarAnyHit) != 0;
+    float tmax = 0.0f;
+    if constexpr (ANY) tmax = t;
+    bool found = false;                 // kVarAnyHit: the walk's result
+    (void)tmax;
+    (void)found;
     float nct0, nct1, nct2, dt0, dt1, dt2;
     int rem0, rem1, rem2, cs0, cs1, cs2, cell;
     // (the ray-query walk with the Newton 1/det but without packed counts: its kernel stands at 63 VGPRs and
@@ -834,7 +887,7 @@ __device__ __forceinline__ bool grid_intersect(const KParams& P, float ox, float
     if (!dda_setup<RCP_SETUP>(P, ox, oy, oz, dx, dy, dz, nct0, nct1, nct2, dt0, dt1, dt2, rem0, rem1, rem2, cs0, cs1,
                               cs2, cell))
         return false;
-    t = rtd::kFltMax;
+    if constexpr (!ANY) t = rtd::kFltMax;
     uint32_t lpar = 0u;                 // kVarLdsSplit: the reduction buffers' parity (test_cell)
 
     if constexpr ((VAR & kVarSkipRun) != 0 && (VAR & kVarPackedRem) != 0)
@@ -899,7 +952,16 @@ __device__ __forceinline__ bool grid_intersect(const KParams& P, float ox, float
             }
             RT_DDA_ADVANCE_BOX(nct_ax, more);
             bool hit = false;
-            if (kb < ke) hit = test_cell<STATS, TRI, VAR>(P, ox, oy, oz, dx, dy, dz, kb, ke, nct_ax, t, u, v, tri, tests, lpar);
+            if (kb < ke) hit = test_cell<STATS, TRI, VAR>(P, ox, oy, oz, dx, dy, dz, kb, ke, nct_ax, t, u, v, tri, tests, lpar, tmin);
+            // kVarAnyHit: the step just taken -- out of a looked-up cell -- crossed at nct_ax; a lane that stops
+            // here takes no run (its box counts are dead: a set guard keeps it out)
+            [[maybe_unused]] bool stop = false;
+            if constexpr (ANY)
+            {
+                found = hit;
+                stop = nct_ax >= tmax;
+                boxw = stop ? kRemGuards : boxw;
+            }
             const bool inside = (uint32_t(boxw) & uint32_t(kRemGuards)) == 0u;
             if (!sync && inside)
             {
@@ -923,6 +985,21 @@ __device__ __forceinline__ bool grid_intersect(const KParams& P, float ox, float
                 while (nct1 < tl && c1 < f1) { nct1 += dt1; c1++; }
                 while (nct2 < tl && c2 < f2) { nct2 += dt2; c2++; }
                 boxw -= c0 + (c1 << 11) + (c2 << 22);
+                if constexpr (ANY)
+                {
+                    // Rule 3 of the any-hit walk asks after EVERY step whether its crossing was >= tmax; inside
+                    // an empty box nothing is tested, so only the cell the run arrives at needs the answer: was
+                    // any crossing of the run >= tmax.  The crossings a walk takes never decrease (each is the
+                    // minimum of three add chains with dt >= 0), the add chains above take only crossings below
+                    // tl, and every bare step's crossing is an untaken one, >= tl: the LAST bare step's
+                    // crossing is the run's largest, and it alone is compared.
+                    float last;
+                    do
+                        RT_DDA_BOX_BARE_STEP_T(last);
+                    while ((uint32_t(boxw) & uint32_t(kRemGuards)) == 0u);
+                    stop = last >= tmax;
+                }
+                else
                 do
                     RT_DDA_BOX_BARE_STEP();
                 while ((uint32_t(boxw) & uint32_t(kRemGuards)) == 0u);
@@ -962,8 +1039,10 @@ __device__ __forceinline__ bool grid_intersect(const KParams& P, float ox, float
                 cell += int(d & 2047u) * cs0 + int((d >> 11) & 2047u) * cs1 + int(d >> 22) * cs2;
                 more = (remp & kRemGuards) == 0;
             }
+            if constexpr (ANY) more &= !stop;
             if (hit | !more) break;
         }
+        if constexpr (ANY) return found;
         // records only: the exit cell in the ray's box-word copy (trace_sample removes the copy's
         // offset, so nothing extra is live across the walk)
         voxel = exit_voxel(remp, cell, cs0, cs1, cs2);
@@ -1005,8 +1084,14 @@ __device__ __forceinline__ bool grid_intersect(const KParams& P, float ox, float
             // below), and the result read from t after the loop: the walk's loop-carried state
             // stays in VGPRs instead of per-exit lane masks (SALU per wave, PMC-measured)
             bool hit = false;
-            if (kb < ke) hit = test_cell<STATS, TRI, VAR>(P, ox, oy, oz, dx, dy, dz, kb, ke, nct_ax, t, u, v, tri, tests, lpar);
+            if (kb < ke) hit = test_cell<STATS, TRI, VAR>(P, ox, oy, oz, dx, dy, dz, kb, ke, nct_ax, t, u, v, tri, tests, lpar, tmin);
             bool done = hit | !more;
+            if constexpr (ANY)
+            {
+                // (one cell per iteration here: every step's crossing is seen)
+                found = hit;
+                done |= nct_ax >= tmax;
+            }
             if constexpr ((VAR & kVarSkipRun) != 0 && (VAR & kVarPackedRem) != 0 && !STATS)
             {
                 // Wave-uniform empty run: while every active lane is inside a run of cells the
@@ -1053,6 +1138,7 @@ __device__ __forceinline__ bool grid_intersect(const KParams& P, float ox, float
             }
             if (done) break;
         }
+        if constexpr (ANY) return found;
         // a lane leaving the grid inside a block of bare steps stepped on: its last cell is lost
         if constexpr (!STATS)
         {
@@ -1074,9 +1160,11 @@ __device__ __forceinline__ bool grid_intersect(const KParams& P, float ox, float
         float nct_ax;
         bool more;
         RT_DDA_ADVANCE_ADD(nct_ax, more);
-        if (kb < ke && test_cell<STATS, TRI, VAR>(P, ox, oy, oz, dx, dy, dz, kb, ke, nct_ax, t, u, v, tri, tests, lpar))
+        if (kb < ke && test_cell<STATS, TRI, VAR>(P, ox, oy, oz, dx, dy, dz, kb, ke, nct_ax, t, u, v, tri, tests, lpar, tmin))
             return true;
         if (!more) break;
+        if constexpr (ANY)
+            if (nct_ax >= tmax) break;
     }
     if constexpr (!STATS) voxel = uint32_t(cell - (rem0 < 0 ? cs0 : (rem1 < 0 ? cs1 : cs2)));   // records only
     return false;

@@ -321,6 +321,40 @@ enum rt_rays_flags {
  *   undefined (a float -> int conversion of NaN, grid.h:46), so this is a definition, not a deviation. */
 int  rt_trace_rays_device(rt_scene *scene, const rt_ray *d_rays, uint32_t n, uint32_t flags,
                           rt_ray_hit *d_hits, rt_sample_rec *d_recs, void *hip_stream);
+/* Occlusion queries (shadow rays, ambient occlusion): is anything hit inside the open interval (tmin, tmax) of
+ * ray i?  One byte per ray, d_occluded[i] = 1 / 0, in input order; exactly n bytes are written.
+ * d_tminmax: [n][2] floats (tmin, tmax) per ray, 8-byte aligned, or NULL = (-inf, +inf) for every ray.
+ *
+ * Ray i is occluded iff this walk returns true.  It is Grid::Intersect (grid.cpp:159-281) with IntersectRayTri
+ * (triangle.h:15-107), unchanged but for three additions:
+ *   1. a test counts iff  hit && cur_t < next_crossing_t[step_axis] && tmin < cur_t && cur_t < tmax  (both
+ *      bounds strict): the reference's own condition (grid.cpp:258-260) without its closer-than-previous clause;
+ *   2. the first test that counts ends the walk with TRUE: no minimum is formed, the rest of the cell's list
+ *      and every later cell are irrelevant (grid.cpp:270, "a hit in this cell ends the walk", without the minimum);
+ *   3. after a cell with no counted test and before the advance (grid.cpp:274):
+ *      if (next_crossing_t[step_axis] >= tmax) return false;  -- exactly '>=' on the f32 crossing time of the
+ *      step about to be taken.  A NaN crossing does not end the walk; the grid's bounds do, as ever.
+ * Everything else is the reference's: the box entry, ToVoxel, the crossing times, cell order, list order, d used
+ * as passed (NOT normalised, so t is in units of |d|: d = light - p puts the light at t = 1), the absolute 1e-8
+ * det gate, t >= 0.  Hence:
+ *   - with tmin = -inf and tmax = +inf the result is Grid::Intersect's return value, bit for bit;
+ *   - with tmin = -inf, occluded implies closest.hit && closest.t < tmax for rt_trace_rays_device's closest hit:
+ *     a cell whose accepted hits all lie at or beyond tmax has an exit crossing above them, so rule 3 ends the
+ *     walk there.  The converse can fail only for a hit the reference accepts in a cell the ray enters at or
+ *     after tmax (float fuzz at cell planes): this is a definition, as the non-finite rule below is;
+ *   - with tmin set the walk goes on past cells whose only hits lie at or before tmin (a ray that starts on a
+ *     surface and skips it), which no filtering of the closest hit can do: that hit ends the closest-hit walk
+ *     and may hide a blocker further on;
+ *   - 0 without a walk: a ray with any non-finite component (as rt_trace_rays_device), a NaN tmin or tmax,
+ *     !(tmin < tmax).  -inf and +inf are legal bounds.
+ * flags: 0 or RT_RAYS_SORT (the same sort, scratch and serialisation as rt_trace_rays_device; the same bytes in
+ * input order).  RT_RAYS_COUNT or an unknown bit: RT_E_INVALID, nothing written.  Otherwise the argument rules
+ * are rt_trace_rays_device's: n == 0 is RT_OK and writes nothing, n < 2^31, NULL or misaligned d_rays, a
+ * misaligned d_tminmax and a NULL d_occluded are RT_E_INVALID before any launch.  Asynchronous on hip_stream.
+ * Without RT_RAYS_SORT the call is stateless: no lock, no event, no allocation, only arrays rt_scene_create
+ * wrote are read, and it needs no ordering against the scene's render launches.  DESIGN.md §4.29 */
+int  rt_occluded_rays_device(rt_scene *scene, const rt_ray *d_rays, const float *d_tminmax, uint32_t n,
+                             uint32_t flags, uint8_t *d_occluded, void *hip_stream);
 /* The frame's width * height * spp camera rays in (y, x, sample) order into d_rays: origin and direction
  * exactly as the render kernels form them (GenerateRay, camera.h:8-47, over the frame's tables), i.e. the
  * bits the frames are traced with -- the start of a bounce.  A launch of the scene like a render call

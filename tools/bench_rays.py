@@ -18,7 +18,11 @@ spread (max - min) / median of the five:
 lock-step walk was measured, profiles/rays_walk_ab.json), samples interleaved with this build's, and checks
 that its results are the same bits.
 
+--occlusion measures rt_occluded_rays_device (GpuScene.occluded) instead, against trace_rays on the same rays in the
+same session, into profiles/occlusion_bench.json (occlusion_legs).
+
     python3 tools/bench_rays.py --parent-lib librt_tracer_parent.so [--ab-lib other=librt_tracer_other.so]
+    python3 tools/bench_rays.py --occlusion
 """
 import argparse
 import importlib.util
@@ -105,6 +109,73 @@ def ao_rays(rays, hits, tri_n, ext, seed=43):
     return torch.cat([p, v], 1).contiguous()
 
 
+def occlusion_legs(args):
+    """--occlusion: rt_occluded_rays_device (GpuScene.occluded) against rt_trace_rays_device ON THE SAME RAYS, the two
+    arms' samples interleaved (measure), into profiles/occlusion_bench.json:
+      camera order and shuffled (PCG64(41)) over the infinite interval;
+      the ambient-occlusion bounce of leg (c) with tmin = 1e-4 x the box diagonal and tmax = +inf / 0.1 x the diagonal;
+      the bounce with RT_RAYS_SORT in both arms.
+    Per leg: both arms' ms, rays/s and spread, speedup = trace ms / occluded ms, and `slower`: the occlusion arm is
+    slower by more than the larger spread.  `consistent`: over the infinite interval the bytes equal the closest
+    call's hit; with an interval they imply it (include/rt_tracer.h)."""
+    rtm = load("rtm_this", None)
+    res = {"tool": "tools/bench_rays.py --occlusion", "frame": [W, H, SPP], "steps": args.steps, "warmup": args.warmup,
+           "samples": 5, "build_hash": rtm.library_build_hash(), "device": torch.cuda.get_device_name(0), "scenes": {}}
+    st = torch.cuda.current_stream().cuda_stream
+    n = W * H * SPP
+    for sid in args.scenes:
+        hs = rtm.HostScene.load(sid)
+        gs = rtm.GpuScene(hs, 0)
+        rays = gs.primary_rays(gs.frame(W, H, SPP))
+        torch.cuda.synchronize()
+        meta = hs.grid()[0]
+        e = (meta["aabb_max"] - meta["aabb_min"]).astype(np.float64)
+        diag = float(np.sqrt((e * e).sum()))
+        entry = {"box_diagonal": diag}
+
+        def leg(r, tmin=None, tmax=None, sort=False):
+            tmm = None
+            if tmin is not None:
+                tmm = torch.empty((r.shape[0], 2), dtype=torch.float32, device=r.device)
+                tmm[:, 0], tmm[:, 1] = tmin, tmax
+            hit = gs.trace_rays(r).hits[:, 0] != -1
+            occ = gs.occluded(r, tmm) != 0
+            same_sorted = bool(torch.equal(gs.occluded(r, tmm, sort=True) != 0, occ))
+            consistent = bool(torch.equal(occ, hit)) if tmm is None else bool((hit | ~occ).all())
+            out = measure({"trace_rays": lambda: gs.trace_rays(r, sort=sort, stream=st),
+                           "occluded": lambda: gs.occluded(r, tmm, sort=sort, stream=st)}, r.shape[0], args.steps, args.warmup)
+            for k in out:
+                out[k]["unit"] = "rays/s"
+            a, b = out["trace_rays"], out["occluded"]
+            spread = max(a["spread"], b["spread"])
+            return {"rays": int(r.shape[0]), "closest_hits": int(hit.sum()), "occluded": int(occ.sum()),
+                    "tmin": tmin, "tmax": None if tmax is None else (tmax if np.isfinite(tmax) else "inf"), "sort": sort,
+                    "consistent": consistent, "sorted_same_bytes": same_sorted, **out,
+                    "speedup": round(a["ms"] / b["ms"], 3), "larger_spread": spread,
+                    "slower": bool(b["ms"] > a["ms"] * (1.0 + spread))}
+
+        entry["camera_order"] = leg(rays)
+        perm = torch.from_numpy(np.random.Generator(np.random.PCG64(41)).permutation(n)).cuda()
+        entry["shuffled"] = leg(rays[perm].contiguous())
+        v, t = hs.mesh()
+        tri_n = torch.from_numpy(np.ascontiguousarray(t[:, 3:6]).view(np.float32).copy()).cuda()
+        ao = ao_rays(rays, gs.trace_rays(rays).hits, tri_n, float((meta["aabb_max"] - meta["aabb_min"]).max()))
+        tmin, short = 1e-4 * diag, 0.1 * diag
+        entry["ao_tmax_inf"] = leg(ao, tmin, float("inf"))
+        entry["ao_tmax_short"] = leg(ao, tmin, short)
+        entry["ao_tmax_inf_sorted"] = leg(ao, tmin, float("inf"), sort=True)
+        entry["ao_tmax_short_sorted"] = leg(ao, tmin, short, sort=True)
+        res["scenes"][str(sid)] = entry
+        print(json.dumps({str(sid): entry}), flush=True)
+        gs.close()
+        hs.close()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print("wrote", args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", type=int, nargs="+", default=[8, 1])
@@ -112,10 +183,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--parent-lib", default=None, help="the parent commit's librt_tracer.so (file in the package directory)")
     ap.add_argument("--ab-lib", action="append", default=[], help="NAME=LIB: the ray legs from another build too")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rays_bench.json"))
+    ap.add_argument("--occlusion", action="store_true", help="the occlusion legs (occlusion_legs) instead of the ray legs")
+    ap.add_argument("--out", default=None, help="default: profiles/rays_bench.json (--occlusion: profiles/occlusion_bench.json)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "occlusion_bench.json" if args.occlusion else "rays_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_rays.py measures on the GPU; none is visible")
+    if args.occlusion:
+        return occlusion_legs(args)
     mods = {"this": load("rtm_this", None)}
     for spec in args.ab_lib:
         name, lib = spec.split("=", 1)
