@@ -26,7 +26,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 KERNEL_SOURCES = ("csrc/rt_kernels.hip", "csrc/rt_walk.h", "csrc/rt_kparams.h", "csrc/rt_plan.hip",
                   "csrc/rt_scene.h", "csrc/rt_tracer.hip", "csrc/rt_grid_build.hip", "csrc/rt_device.h",
                   "csrc/rt_internal.h", "csrc/rt_box_words.h", "csrc/rt_fref_slots.h", "csrc/rt_record_gate.h", "csrc/rt_setup_div.h", "csrc/rt_rays.hip",
-                  "csrc/rt_ray_common.h", "csrc/rt_occlusion.hip", "csrc/Makefile",
+                  "csrc/rt_ray_common.h", "csrc/rt_occlusion.hip", "csrc/rt_ao.hip", "csrc/Makefile",
                   "../include/rt_tracer.h")
 
 
@@ -56,6 +56,8 @@ RT_ISECT_GRID = 0
 RT_ISECT_BRUTE_FORCE = 1
 RT_ISECT_RAY_MARCH = 2
 RT_RAYS_COUNT, RT_RAYS_SORT = 1, 2      # rt_trace_rays_device flags
+RT_AO_ROTATE = 1                        # rt_render_ao_device flags
+AO_MAX_DIRS = 64
 SHARD_TILE = 16
 
 # Symbols of include/rt_tracer.h and include/rt_host.h (checked by tests/test_abi.py)
@@ -69,6 +71,7 @@ TRACER_SYMBOLS = [
     "rt_host_free", "rt_render_hits_device", "rt_scene_info_get", "rt_build_hash", "rt_render_batch_device",
     "rt_render_records_device", "rt_render_frame_host_tiled", "rt_fref_buffer_bytes",
     "rt_trace_rays_device", "rt_primary_rays_device", "rt_occluded_rays_device",
+    "rt_ao_table", "rt_ao_rotations", "rt_render_ao_device",
 ]
 MAX_BATCH = 10                           # frames per rt_render_batch_device launch (kMaxBatch)
 
@@ -130,6 +133,11 @@ class Ray(ctypes.Structure):                # rt_ray, 24 B
 
 class RayHit(ctypes.Structure):             # rt_ray_hit, 16 B
     _fields_ = [("tri", c_u32), ("t", c_f32), ("u", c_f32), ("v", c_f32)]
+
+
+class AoParams(ctypes.Structure):           # rt_ao_params
+    _fields_ = [("num_dirs", c_u32), ("tmin", c_f32), ("tmax", c_f32), ("dirs", ctypes.POINTER(c_f32)),
+                ("flags", c_u32)]
 
 
 class SceneStats(ctypes.Structure):
@@ -209,6 +217,10 @@ def tracer_lib():
             L.rt_primary_rays_device.argtypes = [vp, ctypes.POINTER(Frame), vp, vp]
         if hasattr(L, "rt_occluded_rays_device"):    # absent in earlier builds (A/B runs)
             L.rt_occluded_rays_device.argtypes = [vp, vp, vp, c_u32, c_u32, vp, vp]
+        if hasattr(L, "rt_render_ao_device"):        # absent in earlier builds (A/B runs)
+            L.rt_ao_table.argtypes = [c_u32, vp]
+            L.rt_ao_rotations.argtypes = [vp]
+            L.rt_render_ao_device.argtypes = [vp, ctypes.POINTER(Frame), ctypes.POINTER(AoParams), vp, vp, vp]
         L.rt_unshard_device.argtypes = [c_u32, c_u32, c_u32, vp, vp, vp]
         L.rt_last_kernel_ms.argtypes = [vp, ctypes.POINTER(c_f32)]
         L.rt_trace_samples.argtypes = [vp, ctypes.POINTER(Frame), c_u32, c_u32, c_u32, c_u32, vp]
@@ -328,6 +340,45 @@ def sample_table(spp):
     L = tracer_lib()
     _check(L.rt_sample_table(spp, _ptr(out)), L, "rt_sample_table")
     return out.reshape(spp, 2)
+
+
+def ao_table(K):
+    """rt_ao_table: the K built-in cosine-weighted AO directions, float32 [K, 3] (local frame, z = the normal).
+    Needs no GPU."""
+    if not 1 <= int(K) <= AO_MAX_DIRS:
+        raise ValueError(f"K must be in [1, {AO_MAX_DIRS}]")
+    out = np.zeros(3 * int(K), np.float32)
+    L = tracer_lib()
+    _check(L.rt_ao_table(int(K), _ptr(out)), L, "rt_ao_table")
+    return out.reshape(int(K), 3)
+
+
+def ao_rotations():
+    """rt_ao_rotations: the 16 (cos, sin) pairs RT_AO_ROTATE uses, float32 [16, 2].  Needs no GPU."""
+    out = np.zeros(32, np.float32)
+    L = tracer_lib()
+    _check(L.rt_ao_rotations(_ptr(out)), L, "rt_ao_rotations")
+    return out.reshape(16, 2)
+
+
+def ao_params(num_dirs=4, tmin=0.0, tmax=float("inf"), dirs=None, rotate=True):
+    """A checked rt_ao_params (and the array that keeps its dirs alive): ValueError for what
+    rt_render_ao_device would reject."""
+    if dirs is not None:
+        dirs = np.ascontiguousarray(dirs)
+        if dirs.dtype != np.float32 or dirs.ndim != 2 or dirs.shape[1] != 3:
+            raise ValueError("dirs: a float32 array of shape [K, 3]")
+        if not np.isfinite(dirs).all():
+            raise ValueError("dirs: every entry must be finite")
+        num_dirs = dirs.shape[0]
+    if isinstance(num_dirs, bool) or int(num_dirs) != num_dirs or not 1 <= int(num_dirs) <= AO_MAX_DIRS:
+        raise ValueError(f"num_dirs must be an integer in [1, {AO_MAX_DIRS}]")
+    tmin, tmax = float(np.float32(tmin)), float(np.float32(tmax))
+    if tmin != tmin or tmax != tmax or not tmin < tmax:
+        raise ValueError("tmin < tmax is required, and neither may be NaN")
+    p = AoParams(int(num_dirs), tmin, tmax, dirs.ctypes.data_as(ctypes.POINTER(c_f32)) if dirs is not None else None,
+                 RT_AO_ROTATE if rotate else 0)
+    return p, dirs
 
 
 # ------------------------------------------------------------------ mesh ingestion
@@ -808,6 +859,49 @@ class GpuScene:
                 torch.cuda.synchronize(dev)            # the copy below runs on torch's stream
             return occ.cpu().numpy().astype(bool)
         return occ
+
+    def render_ao(self, frame, num_dirs=4, tmin=0.0, tmax=float("inf"), dirs=None, rotate=True, out=None,
+                  counts=False, stream=None):
+        """rt_render_ao_device: an ambient-occlusion frame in one launch (include/rt_tracer.h has the contract op by
+        op): per sample the camera ray, its closest hit and num_dirs AO rays over the open interval (tmin, tmax);
+        per pixel the render kernels' resolve.
+
+        dirs: None = ao_table(num_dirs), or a float32 [K, 3] host array of local directions (z = the normal; used
+        as passed, K replaces num_dirs).  rotate: RT_AO_ROTATE.  tmin: what skips the surface the rays start on --
+        choose it from the scene's size (1e-4 x the box diagonal is the tools' choice).
+        Returns a torch.uint32 [H, W] tensor on the scene's device (written in place when `out` is given: uint32
+        or int32, contiguous, that shape and device); with counts=True also a torch.uint8 [H, W, spp] tensor of
+        the occluded rays per sample (0xFF: the camera ray hits nothing).  Asynchronous on `stream` (None: torch's
+        current stream).  Bad inputs raise ValueError before any launch."""
+        import torch
+        p, keep = ao_params(num_dirs, tmin, tmax, dirs, rotate)
+        spp = max(1, frame.spp)
+        if spp & (spp - 1) or spp > 64:
+            raise ValueError("render_ao: spp must be a power of two <= 64")
+        if frame.intersector != RT_ISECT_GRID or frame.tri_test != RT_TRI_MOLLER_TRUMBORE:
+            raise ValueError("render_ao: RT_ISECT_GRID and RT_TRI_MOLLER_TRUMBORE only")
+        if frame.width * frame.height * spp >= 2 ** 31:
+            raise ValueError("render_ao: more than 2^31 - 1 samples")
+        dev = torch.device(f"cuda:{self.device}")
+        u32 = getattr(torch, "uint32", torch.int32)
+        if out is None:
+            out = torch.empty((frame.height, frame.width), dtype=u32, device=dev)
+        elif (not isinstance(out, torch.Tensor) or out.dtype not in (u32, torch.int32) or not out.is_cuda or
+              out.device.index != self.device or tuple(out.shape) != (frame.height, frame.width) or
+              not out.is_contiguous()):
+            raise ValueError(f"out: a contiguous uint32 / int32 tensor of shape [H, W] on cuda:{self.device}")
+        cnt = torch.empty((frame.height, frame.width, spp), dtype=torch.uint8, device=dev) if counts else None
+        if stream is not None and int(stream) != torch.cuda.current_stream(dev).cuda_stream:
+            ext = torch.cuda.ExternalStream(int(stream), device=dev)     # (as trace_rays)
+            for o in (out, cnt):
+                if o is not None:
+                    o.record_stream(ext)
+        L = tracer_lib()
+        _check(L.rt_render_ao_device(self._h, ctypes.byref(frame), ctypes.byref(p), ctypes.c_void_p(out.data_ptr()),
+                                     ctypes.c_void_p(cnt.data_ptr() if counts else 0),
+                                     ctypes.c_void_p(self._stream(torch, stream))), L, "rt_render_ao_device")
+        del keep
+        return (out, cnt) if counts else out
 
     def close(self):
         if getattr(self, "_h", None):

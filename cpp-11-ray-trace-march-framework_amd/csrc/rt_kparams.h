@@ -329,5 +329,25 @@ uint32_t ray_key_bits();                        // ... which are sorted by this 
 // kVarAnyHit; tminmax null: (-inf, +inf) for every ray
 using occluded_fn = void (*)(KParams, const float2 *, const float2 *, const unsigned long long *, uint32_t, uint8_t *);
 occluded_fn occluded_rays_kernel(int var);
+// rt_ao.hip: k_render_ao<var>(KAo) -- var: k_trace_rays' fast-arm variant (the AO rays take it | kVarAnyHit).  The
+// frame's KParams and the AO parameters are ONE kernel argument, so the directions and rotations are read from
+// the kernarg segment by scalar loads (and re-read after the walks, as late_params does it).
+constexpr uint32_t kAoMaxDirs = 64;
+struct AoParams
+{
+    uint32_t num_dirs, flags;           // K in [1, kAoMaxDirs]; rt_ao_flags
+    float tmin, tmax;                   // tmin < tmax, neither NaN (rt_render_ao_device checks)
+    uint8_t *counts;                    // [(y*W + x)*spp + s] or null
+    float rot[32];                      // rt_ao_rotations: 16 x (cos, sin)
+    float dirs[3 * kAoMaxDirs];         // the local directions, [K][3]
+};
+struct KAo
+{
+    KParams p;
+    AoParams a;
+};
+static_assert(sizeof(KAo) <= 4096, "kernel arguments");
+using ao_fn = void (*)(KAo);
+ao_fn render_ao_kernel(int var);
 
 } // namespace rtk

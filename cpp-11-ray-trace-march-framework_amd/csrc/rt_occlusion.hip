@@ -16,16 +16,6 @@
 namespace rtk {
 namespace {
 
-template <int VAR>
-__device__ __forceinline__ bool occlusion_walk(const KParams& P, float ox, float oy, float oz, float dx, float dy, float dz,
-                                               float tmin, float tmax)
-{
-    float t = tmax, u = 0.0f, v = 0.0f;            // t carries tmax into the walk (grid_intersect)
-    uint32_t tri = rtd::kNoTri, voxel = rtd::kNoTri, steps = 0, tests = 0;
-    return grid_intersect<false, RT_TRI_MOLLER_TRUMBORE, VAR>(P, ox, oy, oz, dx, dy, dz, t, u, v, tri, voxel, steps, tests,
-                                                              tmin);
-}
-
 // rays, order: as k_trace_rays.  tminmax: (tmin, tmax) per ray, or null = (-inf, +inf).  occluded[i] = 1 / 0.
 template <int VAR>
 __global__ void __launch_bounds__(kWG) k_occluded_rays(KParams P, const float2 *rays, const float2 *tminmax,

@@ -1,5 +1,5 @@
 // rt_ray_common.h -- what the ray-query translation units share (rt_rays.hip: rt_trace_rays_device;
-// rt_occlusion.hip: rt_occluded_rays_device) beside rt_walk.h's walk.
+// rt_occlusion.hip: rt_occluded_rays_device; rt_ao.hip: rt_render_ao_device) beside rt_walk.h's walk.
 #pragma once
 #include "rt_walk.h"
 
@@ -26,6 +26,27 @@ constexpr uint32_t kKeyBits = 32;
 // the ray kernels' variants: kRaysBase [| kVarFastRcp] [| kRaysBox] (rt_tracer.hip scene_traversal_bits)
 constexpr int kRaysBase = kVarRays | kVarWaveGate | kVarDistSkip;
 constexpr int kRaysBox = kVarPackedRem | kVarSkipRun;
+
+// The closest-hit walk of one caller-supplied ray (k_trace_rays' fast arm; k_render_ao's camera ray): the stateless
+// walk over the scene's 48-byte reference records
+template <int VAR>
+__device__ __forceinline__ bool rays_walk(const KParams& P, float ox, float oy, float oz, float dx, float dy, float dz,
+                                          float& t, float& u, float& v, uint32_t& tri)
+{
+    uint32_t voxel = rtd::kNoTri, steps = 0, tests = 0;
+    return grid_intersect<false, RT_TRI_MOLLER_TRUMBORE, VAR>(P, ox, oy, oz, dx, dy, dz, t, u, v, tri, voxel, steps, tests);
+}
+
+// The any-hit walk of one ray over (tmin, tmax) (k_occluded_rays; k_render_ao's AO rays): VAR carries kVarAnyHit
+template <int VAR>
+__device__ __forceinline__ bool occlusion_walk(const KParams& P, float ox, float oy, float oz, float dx, float dy, float dz,
+                                               float tmin, float tmax)
+{
+    float t = tmax, u = 0.0f, v = 0.0f;            // t carries tmax into the walk (grid_intersect)
+    uint32_t tri = rtd::kNoTri, voxel = rtd::kNoTri, steps = 0, tests = 0;
+    return grid_intersect<false, RT_TRI_MOLLER_TRUMBORE, VAR>(P, ox, oy, oz, dx, dy, dz, t, u, v, tri, voxel, steps, tests,
+                                                              tmin);
+}
 
 } // namespace
 } // namespace rtk

@@ -41,14 +41,6 @@ __device__ __forceinline__ uint32_t spread3(uint32_t v)      // 9 bits -> every 
     return v;
 }
 
-template <int VAR>
-__device__ __forceinline__ bool rays_walk(const KParams& P, float ox, float oy, float oz, float dx, float dy, float dz,
-                                          float& t, float& u, float& v, uint32_t& tri)
-{
-    uint32_t voxel = rtd::kNoTri, steps = 0, tests = 0;
-    return grid_intersect<false, RT_TRI_MOLLER_TRUMBORE, VAR>(P, ox, oy, oz, dx, dy, dz, t, u, v, tri, voxel, steps, tests);
-}
-
 // rays: rt_ray as three 8-byte words ({ox, oy} {oz, dx} {dy, dz}: the ABI asks for 8-byte alignment).
 // COUNT: the counting walk of k_trace_records with its full record; else the fast arm (VAR).
 // order (RT_RAYS_SORT; else null): lane k of the launch traces ray order[k] >> kKeyBits and writes that ray's

@@ -1079,6 +1079,42 @@ int rt_sample_table(uint32_t spp, float *out_xy)
     return RT_OK;
 }
 
+// The built-in AO directions (include/rt_tracer.h): cosine-weighted over the Hammersley points (i + 0.5) / K and
+// the base-2 radical inverse of i (hammersley's), in double, rounded once to float.
+int rt_ao_table(uint32_t K, float *out_xyz)
+{
+    if (!out_xyz || K == 0 || K > rtk::kAoMaxDirs) return fail(RT_E_INVALID, "rt_ao_table: K must be in [1, 64]");
+    const double two_pi = 6.283185307179586476925286766559;
+    for (uint32_t i = 0; i < K; i++)
+    {
+        double val = 0.0, inv_i = 0.5;
+        for (uint32_t n = i; n > 0; n /= 2)
+        {
+            val += (n % 2) * inv_i;
+            inv_i *= 0.5;
+        }
+        const double u = (double(i) + 0.5) / double(K), r = std::sqrt(u);
+        out_xyz[3 * i + 0] = float(r * std::cos(two_pi * val));
+        out_xyz[3 * i + 1] = float(r * std::sin(two_pi * val));
+        out_xyz[3 * i + 2] = float(std::sqrt(1.0 - u));
+    }
+    return RT_OK;
+}
+
+// RT_AO_ROTATE's 16 (cos, sin) pairs: angles 2 pi (j + 0.5) / 16, in double, rounded once to float
+int rt_ao_rotations(float *out_cs)
+{
+    if (!out_cs) return fail(RT_E_INVALID, "rt_ao_rotations: NULL argument");
+    const double two_pi = 6.283185307179586476925286766559;
+    for (uint32_t j = 0; j < 16; j++)
+    {
+        const double a = two_pi * (double(j) + 0.5) / 16.0;
+        out_cs[2 * j + 0] = float(std::cos(a));
+        out_cs[2 * j + 1] = float(std::sin(a));
+    }
+    return RT_OK;
+}
+
 // Cap on the 8 octant copies of the cell words (device and host): 64 M cells at most.
 constexpr uint64_t kOctWordsMaxBytes = 256ull << 20;
 // ... and on the 24 box-run copies
@@ -2176,6 +2212,76 @@ int rt_primary_rays_device(rt_scene *s, const rt_frame *f, rt_ray *d_rays, void 
     RT_HIP(hipEventRecord(s->ev_own->ev, st));
     s->ev_last = s->ev_own;
     s->ev_recorded = true;
+    return RT_OK;
+}
+
+// An AO frame in one launch of k_render_ao (rt_ao.hip; include/rt_tracer.h has the contract).  Every argument is
+// checked before the scene is touched.  The launch itself is rt_primary_rays_device's: a launch of the scene
+// that reads its frame tables and no per-origin records.  The directions and rotations are kernel arguments.
+int rt_render_ao_device(rt_scene *s, const rt_frame *f, const rt_ao_params *ao, uint32_t *d_bgra, uint8_t *d_counts,
+                        void *hip_stream)
+{
+    if (!s) return fail(RT_E_INVALID, "scene is NULL");
+    if (!f) return fail(RT_E_INVALID, "frame is NULL");
+    if (!ao) return fail(RT_E_INVALID, "ao is NULL");
+    if (!d_bgra) return fail(RT_E_INVALID, "d_bgra is NULL");
+    int rc = validate_frame(f);
+    if (rc) return rc;
+    if (ao->num_dirs == 0 || ao->num_dirs > rtk::kAoMaxDirs) return fail(RT_E_INVALID, "num_dirs must be in [1, 64]");
+    if (std::isnan(ao->tmin) || std::isnan(ao->tmax)) return fail(RT_E_INVALID, "tmin / tmax is NaN");
+    if (!(ao->tmin < ao->tmax)) return fail(RT_E_INVALID, "tmin must be below tmax");
+    if (ao->flags & ~uint32_t(RT_AO_ROTATE)) return fail(RT_E_INVALID, "unknown rt_ao_flags bit");
+    const uint32_t spp = std::max(1u, f->spp);
+    if (!(is_pow2(spp) && spp <= 64)) return fail(RT_E_INVALID, "rt_render_ao_device needs spp to be a power of two <= 64");
+    if (f->intersector != RT_ISECT_GRID || f->tri_test != RT_TRI_MOLLER_TRUMBORE)
+        return fail(RT_E_INVALID, "rt_render_ao_device needs RT_ISECT_GRID and RT_TRI_MOLLER_TRUMBORE");
+    const uint64_t n64 = uint64_t(f->width) * f->height * spp;
+    if (n64 >= 0x80000000ull) return fail(RT_E_INVALID, "more than 2^31 - 1 samples");
+    rtk::KAo G;
+    std::memset(&G.a, 0, sizeof(G.a));
+    G.a.num_dirs = ao->num_dirs;
+    G.a.flags = ao->flags;
+    G.a.tmin = ao->tmin;
+    G.a.tmax = ao->tmax;
+    G.a.counts = d_counts;
+    if (ao->dirs)
+    {
+        for (uint32_t i = 0; i < 3u * ao->num_dirs; i++)
+        {
+            if (!std::isfinite(ao->dirs[i])) return fail(RT_E_INVALID, "dirs holds a non-finite entry");
+            G.a.dirs[i] = ao->dirs[i];
+        }
+    }
+    else if ((rc = rt_ao_table(ao->num_dirs, G.a.dirs)))
+        return rc;
+    if ((rc = rt_ao_rotations(G.a.rot))) return rc;
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if ((rc = ensure_device(s))) return rc;
+    if ((rc = prepare_samples(s, f, spp))) return rc;
+    KParams& P = G.p;
+    const uint32_t tiles = device_params(s, f, 0u, 1u, false, d_bgra, nullptr, P);
+    P.frefs = nullptr;                  // per-camera-origin state: not this path's (as rt_trace_rays_device)
+    P.gates = nullptr;
+    P.wg_per_tile = (kTilePix * spp) / kWG;             // = spp: one wave per 64 sample slots of a tile
+    P.ipt_shift = log2u(P.wg_per_tile * kWavesPerWG);
+    P.tiles_x_m = udiv_magic(P.tiles_x);
+    const uint64_t blocks = uint64_t(tiles) * P.wg_per_tile;
+    if (blocks > 0x3FFFFFFFull) return fail(RT_E_INVALID, "frame too large for one launch");
+    const int var = kVarRays | kVarWaveGate | kVarDistSkip | scene_traversal_bits(s);
+    const rtk::ao_fn fn = rtk::render_ao_kernel(var);
+    if (!fn) return fail(RT_E_INVALID, "kernel variant not built: " + std::to_string(var));
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if ((rc = order_all(s, st))) return rc;
+    if ((rc = flush_tables(s, st))) return rc;
+    s->last_stream = st;
+    rtk::fref_launched(s->fref, 0u);            // (this launch reads no per-origin records)
+    // the dispatch carries the scene's completion event, an event nothing still holds (launch_render's plain arm):
+    // the predecessor's event, which order_all kept as ev_prev, stays what it was, so a capture of this call after
+    // ONE warm-up queries no event recorded on the capturing stream
+    if ((rc = free_done_event(s, s->ev_last))) return rc;
+    hipExtLaunchKernelGGL(fn, dim3(uint32_t(blocks)), dim3(kWG), 0, st, nullptr, s->ev_last->ev, 0u, G);
+    s->ev_recorded = true;
+    RT_HIP(hipGetLastError());
     return RT_OK;
 }
 

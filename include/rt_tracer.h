@@ -361,6 +361,64 @@ int  rt_occluded_rays_device(rt_scene *scene, const rt_ray *d_rays, const float 
  * (it may rewrite the scene's frame tables), asynchronous on hip_stream. */
 int  rt_primary_rays_device(rt_scene *scene, const rt_frame *frame, rt_ray *d_rays, void *hip_stream);
 
+/* ---- ambient-occlusion frames -------------------------------------------------------- */
+enum rt_ao_flags {
+    RT_AO_ROTATE = 1        /* rotate the local directions about the normal, per pixel position and sample */
+};
+typedef struct rt_ao_params {
+    uint32_t     num_dirs;  /* K, 1..64 */
+    float        tmin, tmax;/* the open interval of every AO ray, in units of |w| (|w| ~ 1 for unit dirs) */
+    const float *dirs;      /* HOST [K][3], local frame (z = the normal), or NULL = rt_ao_table(K); read during
+                               the call only: the library keeps no pointer */
+    uint32_t     flags;     /* rt_ao_flags */
+} rt_ao_params;
+/* The built-in K cosine-weighted directions, K in 1..64: (sqrt(u) cos 2 pi v, sqrt(u) sin 2 pi v, sqrt(1 - u))
+ * with u = (i + 0.5) / K and v = the base-2 radical inverse of i (the Hammersley points of rt_sample_table),
+ * computed in double and rounded once to float.  Needs no GPU. */
+int  rt_ao_table(uint32_t K, float *out_xyz);
+/* The 16 (cos, sin) pairs of RT_AO_ROTATE, angles 2 pi (j + 0.5) / 16, computed in double and rounded once to
+ * float, into out_cs[16][2].  Needs no GPU. */
+int  rt_ao_rotations(float *out_cs);
+/* An ambient-occlusion frame in ONE launch: per sample the camera ray, its closest hit, K AO rays from the hit
+ * point and the share of them that is open; per pixel the render kernels' resolve.  d_bgra[y*width + x] is one
+ * packed pixel, as rt_render_frame_device writes it.  d_counts (optional, may be NULL): d_counts[(y*width + x)*spp
+ * + s] = the number of occluded AO rays of that sample, 0xFF for a sample whose camera ray hits nothing.
+ *
+ * The contract, per sample (y, x, s).  Every float operation is ONE f32 rounding, there is no FMA, and no
+ * direction is normalised:
+ *   1. (o, d) = the bits rt_primary_rays_device writes for (y, x, s).
+ *   2. (tri, t, u, v) = what rt_trace_rays_device gives for (o, d).
+ *   3. A miss: the colour is the reference's background float(y) / float(height) (renderer.cpp:121).
+ *   4. A hit.  e1 = v1 - v0, e2 = v2 - v0 of triangle tri;
+ *        g = (e1.y*e2.z - e1.z*e2.y, e1.z*e2.x - e1.x*e2.z, e1.x*e2.y - e1.y*e2.x);
+ *        n = g / sqrtf((g.x*g.x + g.y*g.y) + g.z*g.z)   per component;
+ *        if ((n.x*d.x + n.y*d.y) + n.z*d.z > 0) n = -n;
+ *        p = o + t*d   per component (no push off the surface: tmin skips the surface the ray starts on);
+ *      the tangent frame of n (Duff et al. 2017), with sg = copysignf(1, n.z):
+ *        a = -1 / (sg + n.z);   b = (n.x*n.y) * a;
+ *        T1 = (1 + (sg*(n.x*n.x))*a,  sg*b,  -(sg*n.x));
+ *        T2 = (b,  sg + (n.y*n.y)*a,  -n.y).
+ *   5. Direction k of K: (lx, ly, lz) = dirs[k]; with RT_AO_ROTATE (lx, ly) <- (c*lx - s*ly, s*lx + c*ly) for
+ *      (c, s) = rt_ao_rotations[j], j = ((x & 3) | ((y & 3) << 2)) ^ (sample & 15);
+ *        w = (lx*T1 + ly*T2) + lz*n   per component, not renormalised.
+ *   6. AO ray k is occluded iff rt_occluded_rays_device says so for (p, w) over (tmin, tmax): a non-finite p or w
+ *      (a sliver whose g has length 0, an overflow) is therefore unoccluded, without a walk.
+ *   7. With c occluded rays the sample's colour is r = g = b = float(K - c) / float(K).
+ *   8. The pixel: the samples' colours summed in the order s = 0, 1, ..., then the render kernels' own average,
+ *      gamma and ToBGRA8 (renderer.cpp:124-133).
+ * Arguments: NULL scene, frame, ao or d_bgra; num_dirs outside 1..64; a NaN bound or !(tmin < tmax) (-inf and
+ * +inf are legal bounds); a non-finite entry of dirs; an unknown flag; spp that is not a power of two <= 64 (a
+ * pixel's samples are summed across adjacent lanes, as RT_KERNEL_LANES); frame->intersector != RT_ISECT_GRID or
+ * frame->tri_test != RT_TRI_MOLLER_TRUMBORE; more than 2^31 - 1 samples; anything rt_render_frame_device rejects
+ * in a frame: RT_E_INVALID before any launch, nothing written.  frame->kernel is otherwise ignored.
+ * Asynchronous on hip_stream; a launch of the scene exactly as rt_primary_rays_device is (it takes the scene's
+ * mutex, may rewrite the scene's frame tables, is ordered after the scene's earlier launches and is its last
+ * launch).  It allocates nothing once the frame tables fit; dirs and the rotations travel as kernel arguments,
+ * so there is no host-to-device copy and the call can be captured in a graph after one warm-up call of the same
+ * frame.  DESIGN.md §4.30 */
+int  rt_render_ao_device(rt_scene *scene, const rt_frame *frame, const rt_ao_params *ao,
+                         uint32_t *d_bgra, uint8_t *d_counts, void *hip_stream);
+
 /* Render-kernel time of the last timed rendering call on this scene (ms): the HIP events on the
  * launch stream immediately around its render kernel(s), as rt_kernel_times.  Waits for them. */
 int  rt_last_kernel_ms(rt_scene *scene, float *ms);

@@ -21,8 +21,12 @@ that its results are the same bits.
 --occlusion measures rt_occluded_rays_device (GpuScene.occluded) instead, against trace_rays on the same rays in the
 same session, into profiles/occlusion_bench.json (occlusion_legs).
 
+--ao measures rt_render_ao_device (GpuScene.render_ao), the AO frame in one launch, against the composition it fuses
+on the same frame, in the same session, into profiles/ao_bench.json (ao_legs).
+
     python3 tools/bench_rays.py --parent-lib librt_tracer_parent.so [--ab-lib other=librt_tracer_other.so]
     python3 tools/bench_rays.py --occlusion
+    python3 tools/bench_rays.py --ao
 """
 import argparse
 import importlib.util
@@ -176,6 +180,136 @@ def occlusion_legs(args):
     print("wrote", args.out)
 
 
+def ao_compose(rtm, gs, f, dirs, rot, tmin, tmax, e1, e2, st, parts=None):
+    """The composition rt_render_ao_device fuses, on the device: primary_rays -> trace_rays -> the contract's steps 4-5
+    in torch (tests/ao_ref.py's operations, one torch operation each) -> occluded -> counts and the resolve in torch.
+    -> (pixels int32 [H, W], counts uint8 [H, W, spp]).  parts: a dict that receives the AO rays and intervals (for the
+    legs that time the library calls alone)."""
+    Wf, Hf, spp = f.width, f.height, max(1, f.spp)
+    K = dirs.shape[0]
+    rays = gs.primary_rays(f, stream=st)
+    hits = gs.trace_rays(rays, stream=st).hits
+    tri = hits[:, 0]
+    idx = (tri != -1).nonzero().squeeze(1)
+    t = hits[idx, 1].view(torch.float32)
+    o, d = rays[idx, :3], rays[idx, 3:]
+    a, b = e1[tri[idx].long()], e2[tri[idx].long()]
+    g = torch.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2],
+                     a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], 1)
+    n = g / torch.sqrt((g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2])[:, None]
+    flip = ((n[:, 0] * d[:, 0] + n[:, 1] * d[:, 1]) + n[:, 2] * d[:, 2]) > 0
+    n = torch.where(flip[:, None], -n, n)
+    p = o + t[:, None] * d
+    nx, ny, nz = n[:, 0], n[:, 1], n[:, 2]
+    sg = torch.copysign(torch.ones_like(nz), nz)
+    fa = -1.0 / (sg + nz)
+    fb = (nx * ny) * fa
+    t1 = torch.stack([1.0 + (sg * (nx * nx)) * fa, sg * fb, -(sg * nx)], 1)
+    t2 = torch.stack([fb, sg + (ny * ny) * fa, -ny], 1)
+    lx, ly, lz = dirs[None, :, 0], dirs[None, :, 1], dirs[None, :, 2]
+    if rot is not None:
+        s_ = idx % spp
+        x_ = (idx // spp) % Wf
+        y_ = idx // (spp * Wf)
+        j = ((x_ & 3) | ((y_ & 3) << 2)) ^ (s_ & 15)
+        c, sn = rot[j, 0][:, None], rot[j, 1][:, None]
+        lx, ly = c * lx - sn * ly, sn * lx + c * ly
+    w = (lx[:, :, None] * t1[:, None, :] + ly[:, :, None] * t2[:, None, :]) + lz[:, :, None] * n[:, None, :]
+    ao = torch.cat([p[:, None, :].expand(-1, K, -1), w], 2).reshape(-1, 6).contiguous()
+    tmm = torch.empty((ao.shape[0], 2), dtype=torch.float32, device=ao.device)
+    tmm[:, 0], tmm[:, 1] = tmin, tmax
+    if parts is not None:
+        parts["rays"], parts["ao"], parts["tmm"] = rays, ao, tmm
+    occ = gs.occluded(ao, tmm, stream=st)
+    cnt = torch.full((Wf * Hf * spp,), 255, dtype=torch.uint8, device=ao.device)
+    cnt[idx] = occ.view(-1, K).sum(1, dtype=torch.int32).to(torch.uint8)
+    cnt = cnt.view(Hf, Wf, spp)
+    y = torch.arange(Hf, device=ao.device, dtype=torch.float32)[:, None, None]
+    col = torch.where(cnt == 255, (y / float(Hf)).expand(-1, Wf, spp), (float(K) - cnt.to(torch.float32)) / float(K))
+    total = col[:, :, 0]
+    for k in range(1, spp):
+        total = total + col[:, :, k]
+    gch = torch.sqrt(total * (1.0 / spp))
+    ch = torch.where(gch > 1.0, torch.full_like(gch, 255.0), torch.trunc(gch * 255.0)).to(torch.int32) & 255
+    return (ch << 16) | (ch << 8) | ch, cnt
+
+
+def ao_legs(args):
+    """--ao: per scene, K in {4, 16}, tmin = 1e-4 x the box diagonal, tmax = +inf and 0.1 x the diagonal, rotated, the
+    built-in table, into profiles/ao_bench.json.  Arms, samples interleaved (measure), ms per frame:
+      fused            rt_render_ao_device, with d_counts;
+      composition      ao_compose: the three library calls and the torch kernels between them;
+      primary_rays, trace_rays, occluded   each library call of the composition alone, on the composition's own rays.
+    three_call_sum = the last three; fused_over_three_calls and fused_over_composition are ms ratios (below 1: the
+    fused call is faster); `slower_than_three_calls`: by more than the larger spread of
+    fused, trace_rays and occluded.  same_counts / same_pixels: the
+    share of the fused call's bytes / words the composition reproduces (torch's kernels are not held to the
+    contract's roundings; the tests compare against numpy)."""
+    rtm = load("rtm_this", None)
+    res = {"tool": "tools/bench_rays.py --ao", "frame": [W, H, SPP], "steps": args.steps, "warmup": args.warmup,
+           "samples": 5, "build_hash": rtm.library_build_hash(), "device": torch.cuda.get_device_name(0),
+           "arm_b": "removed: the packing arm lost every leg to arm A (DESIGN.md 4.30); the committed "
+                    "profiles/ao_bench.json was written while it existed and holds its figures (fused_pack)", "scenes": {}}
+    st = torch.cuda.current_stream().cuda_stream
+    n = W * H * SPP
+    rot = torch.from_numpy(rtm.ao_rotations()).cuda()
+    for sid in args.scenes:
+        hs = rtm.HostScene.load(sid)
+        gs = rtm.GpuScene(hs, 0)
+        f = gs.frame(W, H, SPP)
+        meta = hs.grid()[0]
+        e = (meta["aabb_max"] - meta["aabb_min"]).astype(np.float64)
+        diag = float(np.sqrt((e * e).sum()))
+        v, t = hs.mesh()
+        pos = np.ascontiguousarray(v[:, :3], np.float32)
+        ti = t[:, :3].astype(np.int64)
+        e1 = torch.from_numpy(pos[ti[:, 1]] - pos[ti[:, 0]]).cuda()
+        e2 = torch.from_numpy(pos[ti[:, 2]] - pos[ti[:, 0]]).cuda()
+        entry = {"box_diagonal": diag}
+        out = torch.empty((H, W), dtype=torch.int32, device="cuda")
+        for K in (4, 16):
+            dirs = torch.from_numpy(rtm.ao_table(K)).cuda()
+            for label, tmax in (("inf", float("inf")), ("short", 0.1 * diag)):
+                tmin = 1e-4 * diag
+                parts = {}
+                pix, cnt = ao_compose(rtm, gs, f, dirs, rot, tmin, tmax, e1, e2, st, parts)
+                fpix, fcnt = gs.render_ao(f, K, tmin, tmax, counts=True)
+                torch.cuda.synchronize()
+                same_c = float((fcnt == cnt).float().mean())
+                same_p = float((fpix.view(torch.int32) == pix).float().mean())
+                rays, ao, tmm = parts["rays"], parts["ao"], parts["tmm"]
+                hit = fcnt != 255
+                m = measure({"fused": lambda: gs.render_ao(f, K, tmin, tmax, out=out, counts=True, stream=st),
+                             "composition": lambda: ao_compose(rtm, gs, f, dirs, rot, tmin, tmax, e1, e2, st),
+                             "primary_rays": lambda: gs.primary_rays(f, stream=st),
+                             "trace_rays": lambda: gs.trace_rays(rays, stream=st),
+                             "occluded": lambda: gs.occluded(ao, tmm, stream=st)}, n, args.steps, args.warmup)
+                for k in m:
+                    m[k]["unit"] = "samples/s"
+                three = m["primary_rays"]["ms"] + m["trace_rays"]["ms"] + m["occluded"]["ms"]
+                # (primary_rays is 0.04 ms of the sum and its spread is launch jitter: it does not enter the comparison)
+                spread = max(m[k]["spread"] for k in ("fused", "trace_rays", "occluded"))
+                entry[f"K{K}_tmax_{label}"] = {
+                    "K": K, "tmin": tmin, "tmax": "inf" if label == "inf" else tmax, "hit_samples": int(hit.sum()),
+                    "ao_rays": int(ao.shape[0]), "occluded_share": round(float(fcnt[hit].float().sum()) / max(1, ao.shape[0]), 4),
+                    "same_counts": round(same_c, 6), "same_pixels": round(same_p, 6), **m,
+                    "three_call_sum_ms": round(three, 4), "fused_over_three_calls": round(m["fused"]["ms"] / three, 3),
+                    "fused_over_composition": round(m["fused"]["ms"] / m["composition"]["ms"], 3), "larger_spread": spread,
+                    "slower_than_three_calls": bool(m["fused"]["ms"] > three * (1.0 + spread)),
+                    "composition_bytes": int(n * 40 + ao.shape[0] * 33), "fused_bytes": int(W * H * 4 + n)}
+                del parts, rays, ao, tmm, pix, cnt
+                torch.cuda.empty_cache()
+        res["scenes"][str(sid)] = entry
+        print(json.dumps({str(sid): entry}), flush=True)
+        gs.close()
+        hs.close()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print("wrote", args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", type=int, nargs="+", default=[8, 1])
@@ -184,12 +318,17 @@ def main():
     ap.add_argument("--parent-lib", default=None, help="the parent commit's librt_tracer.so (file in the package directory)")
     ap.add_argument("--ab-lib", action="append", default=[], help="NAME=LIB: the ray legs from another build too")
     ap.add_argument("--occlusion", action="store_true", help="the occlusion legs (occlusion_legs) instead of the ray legs")
-    ap.add_argument("--out", default=None, help="default: profiles/rays_bench.json (--occlusion: profiles/occlusion_bench.json)")
+    ap.add_argument("--ao", action="store_true", help="the AO-frame legs (ao_legs) instead of the ray legs")
+    ap.add_argument("--out", default=None, help="default: profiles/rays_bench.json (--occlusion: profiles/occlusion_bench.json; "
+                                                "--ao: profiles/ao_bench.json)")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "occlusion_bench.json" if args.occlusion else "rays_bench.json")
+        args.out = os.path.join(ROOT, "profiles", "ao_bench.json" if args.ao else
+                                "occlusion_bench.json" if args.occlusion else "rays_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_rays.py measures on the GPU; none is visible")
+    if args.ao:
+        return ao_legs(args)
     if args.occlusion:
         return occlusion_legs(args)
     mods = {"this": load("rtm_this", None)}
