@@ -765,6 +765,24 @@ int orc_trace_samples(const orc_scene *h, uint32_t W, uint32_t H, uint32_t spp, 
     return 0;
 }
 
+int orc_trace_rays(const orc_scene *h, const float *rays, uint32_t n, uint32_t *recs)
+{
+    if (!h || (n && (!rays || !recs))) return 1;
+    for (uint32_t i=0; i<n; i++)
+    {
+        const float *r = rays + size_t(i) * 6;
+        float t = 0, u = 0, v = 0;
+        uint32_t tri = 0xFFFFFFFFu, voxel = 0xFFFFFFFFu, steps = 0, tests = 0;
+        const bool hit = Intersect(h->s, mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), 0, t, u, v, tri, voxel, steps, tests);
+        if (!hit) { t = u = v = 0.0f; tri = 0xFFFFFFFFu; }
+        uint32_t *o = recs + size_t(i) * 8;
+        o[0] = hit; o[1] = tri;
+        std::memcpy(o + 2, &t, 4); std::memcpy(o + 3, &u, 4); std::memcpy(o + 4, &v, 4);
+        o[5] = voxel; o[6] = steps; o[7] = tests;
+    }
+    return 0;
+}
+
 void orc_hammersley(uint32_t spp, float *out)
 {
     const std::vector<float> t = Hammersley(spp);

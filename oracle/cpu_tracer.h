@@ -65,6 +65,10 @@ int orc_render_cam(const orc_scene *s, uint32_t W, uint32_t H, uint32_t spp, con
 /* Per-sample records for the pixel rectangle [x0,x0+w) x [y0,y0+h), order (y, x, s). */
 int orc_trace_samples(const orc_scene *s, uint32_t W, uint32_t H, uint32_t spp, uint32_t tri_test,
                       uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, orc_rec *out);
+/* Grid::Intersect (Moller-Trumbore) on caller-supplied rays: rays n x 6 f32 (origin, direction as passed),
+ * recs n x 8 words hit, tri, t, u, v, voxel, steps, tests (refdriver's "rays" record; t = u = v = 0 and
+ * tri = 0xFFFFFFFF on a miss, voxel 0xFFFFFFFF when the ray misses the grid box). */
+int orc_trace_rays(const orc_scene *s, const float *rays, uint32_t n, uint32_t *recs);
 
 /* Primitive restatements, vectorised over n records (layouts = tests/golden/kat_*.f32). */
 void orc_hammersley(uint32_t spp, float *out_xy);

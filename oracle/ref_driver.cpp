@@ -29,6 +29,9 @@
 //   alt-samples <scene.rtscene> W H spp x0 y0 w h brute|march <out.bin>
 //                                            records of Renderer::IntersectBruteForce / RayMarch
 //   render ... [--isect grid|brute|march]   the frame with another intersector (renderer.cpp:103-105)
+//   rays <scene.rtscene> <rays.f32> <out.rec>   Grid::Intersect on caller-supplied rays: in n x 6 f32 (origin,
+//                                            direction as passed), out n x 8 words hit, tri, t, u, v, voxel,
+//                                            steps, tests (the last three 0 in the uninstrumented build)
 //   kat <outdir>                             primitive known-answer vectors
 //   kat-dist <out.f32>                       DistancePointTri known answers
 
@@ -519,7 +522,7 @@ bool WriteFile(const char *path, const void *data, size_t bytes)
 
 int Usage()
 {
-    std::fprintf(stderr, "usage: refdriver dump-scenes|grid|render|samples|kat ...\n");
+    std::fprintf(stderr, "usage: refdriver dump-scenes|grid|render|samples|rays|kat ...\n");
     return 2;
 }
 
@@ -833,7 +836,7 @@ int main(int argc, char **argv)
         return CmdKatDist(argv[2]);
 
     if ((cmd == "grid" && (argc == 4 || argc == 5)) || (cmd == "render" && argc >= 6) ||
-        (cmd == "samples" && argc >= 11) || (cmd == "alt-samples" && argc == 12))
+        (cmd == "samples" && argc >= 11) || (cmd == "alt-samples" && argc == 12) || (cmd == "rays" && argc == 5))
     {
         SceneFile sf;
         if (!ReadScene(argv[2], sf)) { std::fprintf(stderr, "bad scene file\n"); return 1; }
@@ -852,6 +855,41 @@ int main(int argc, char **argv)
             grid.Export(f);
             std::fclose(f);
             std::printf("RESULT {\"grid_build_s\": %.6f}\n", build_s);
+            return 0;
+        }
+
+        if (cmd == "rays")
+        {
+            // u32 hit, tri | f32 t, u, v | u32 voxel, steps, tests   (t, u, v = 0 and tri = ~0 on a miss)
+            struct RayRec { uint32 hit, tri; float t, u, v; uint32 voxel, steps, tests; };
+            std::FILE *rf = std::fopen(argv[3], "rb");
+            if (!rf) { std::fprintf(stderr, "bad ray file\n"); return 1; }
+            std::vector<float> in;
+            float six[6];
+            while (std::fread(six, 4, 6, rf) == 6) in.insert(in.end(), six, six + 6);
+            std::fclose(rf);
+            const size_t n = in.size() / 6;
+            std::vector<RayRec> recs(n);
+            for (size_t i=0; i<n; i++)
+            {
+                const Vec3f origin(in[6 * i], in[6 * i + 1], in[6 * i + 2]);
+                const Vec3f dir(in[6 * i + 3], in[6 * i + 4], in[6 * i + 5]);
+                float t = 0, u = 0, v = 0;
+                uint32 tri = 0xFFFFFFFFu;
+#ifdef RT_REF_INSTR
+                g_rt_ref_walk = RtRefWalk{0xFFFFFFFFu, 0u, 0u};
+#endif
+                const bool hit = grid.Intersect(origin, dir, t, u, v, tri);
+                if (!hit) { t = u = v = 0.0f; tri = 0xFFFFFFFFu; }
+                RayRec& r = recs[i];
+                r.hit = hit; r.tri = tri; r.t = t; r.u = u; r.v = v;
+                r.voxel = r.steps = r.tests = 0;
+#ifdef RT_REF_INSTR
+                r.voxel = g_rt_ref_walk.cell; r.steps = g_rt_ref_walk.steps; r.tests = g_rt_ref_walk.tests;
+#endif
+            }
+            if (!WriteFile(argv[4], n ? &recs[0] : nullptr, n * sizeof(RayRec))) return 1;
+            std::printf("RESULT {\"rays\": %zu}\n", n);
             return 0;
         }
 

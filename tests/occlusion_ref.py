@@ -1,13 +1,14 @@
 """A numpy float32 restatement of the walk rt_occluded_rays_device is defined by (include/rt_tracer.h), and of
-Grid::Intersect itself, shared by tests/test_occlusion_cpu.py (which pins it to the reference's records) and
-tests/test_gpu_occlusion.py (which holds the kernel to it, byte for byte).  A plain module, numpy only.
+Grid::Intersect itself, shared by tests/test_occlusion_cpu.py and tests/test_ray_sets_cpu.py (which pin it to the
+reference's records, on camera rays and on rays no camera makes) and tests/test_gpu_occlusion.py and
+tests/test_gpu_ray_sets.py (which hold the kernel to it, byte for byte).  A plain module, numpy only.
 
 Restated from the reference, one float32 operation per reference operation, in its order, nothing fused (two
 numpy ufunc calls cannot contract into an FMA):
   IntersectPointAABB, IntersectRayAABB (aabb.h:9-13, 34-83), ToVoxel / ToPos (grid.h:44-51), the 3D-DDA of
   Grid::Intersect (grid.cpp:159-281), IntersectRayTri's non-culling branch (triangle.h:15-107).
 Vectorised over rays: every ray carries its own walk state, and one outer iteration is one cell of every ray
-still walking; a cell's list is tested position by position, so the order of tests per ray is the reference's.
+still walking; a cell's list is tested as a whole and the outcome taken that testing it in order gives.
 
 mode "closest": Grid::Intersect -> hit, tri, voxel (GridIdx of the accepted cell / the last cell walked;
 0xFFFFFFFF when the ray misses the grid box), t, u, v, and the counts steps (cells visited) and tests (triangles
@@ -26,6 +27,7 @@ FLT_MAX = np.finfo(np.float32).max
 EPS = F(0.00000001)                      # triangle.h:26
 NOTRI = 0xFFFFFFFF
 INT_MIN = -(2 ** 31)
+PAIRS_PER_SLICE = 1 << 19                 # (ray, triangle) tests evaluated at once by walk()
 
 
 class RefScene:
@@ -81,6 +83,30 @@ def ray_tri(o, d, v0, v1, v2):
     return hit, t, u, v
 
 
+def box_entry(sc, o, d):
+    """grid.cpp:174-185, the on-grid origin, on [n, 3] arrays -> (inside, ok, enter_t, grid_intersection):
+    IntersectPointAABB, else IntersectRayAABB's tmin (ok = the slab test's verdict, only meaningful where not inside)."""
+    with np.errstate(all="ignore"):
+        inside = ((o >= sc.bmin) & (o <= sc.bmax)).all(1)                 # IntersectPointAABB
+        inv = F(1.0) / d                                                  # aabb.h:49
+        sign = inv < F(0)
+        lo, hi = np.where(sign, sc.bmax, sc.bmin), np.where(sign, sc.bmin, sc.bmax)
+        t0 = (lo[:, 0] - o[:, 0]) * inv[:, 0]
+        t1 = (hi[:, 0] - o[:, 0]) * inv[:, 0]
+        ty0 = (lo[:, 1] - o[:, 1]) * inv[:, 1]
+        ty1 = (hi[:, 1] - o[:, 1]) * inv[:, 1]
+        ok = ~((t0 > ty1) | (ty0 > t1))
+        t0 = np.where(ty0 > t0, ty0, t0)
+        t1 = np.where(ty1 < t1, ty1, t1)
+        tz0 = (lo[:, 2] - o[:, 2]) * inv[:, 2]
+        tz1 = (hi[:, 2] - o[:, 2]) * inv[:, 2]
+        ok &= ~((t0 > tz1) | (tz0 > t1))
+        t0 = np.where(tz0 > t0, tz0, t0)
+        enter = np.where(inside, F(0), t0).astype(F)
+        g = np.where(inside[:, None], o, o + d * enter[:, None]).astype(F)
+    return inside, ok, enter, g
+
+
 def walk(sc, rays, tminmax=None, mode="closest"):
     """rays [n, 6] f32 (origin, direction as passed); tminmax [n, 2] f32 or None = (-inf, +inf).  Returns a dict of
     per-ray arrays: mode "closest": hit (bool), tri, voxel (u32), t, u, v (f32), steps, tests (u32);
@@ -105,24 +131,7 @@ def walk(sc, rays, tminmax=None, mode="closest"):
     steps, tests = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
 
     with np.errstate(all="ignore"):
-        # ---- grid.cpp:174-185: the on-grid origin
-        inside = ((o >= sc.bmin) & (o <= sc.bmax)).all(1)                 # IntersectPointAABB
-        inv = F(1.0) / d                                                  # aabb.h:49
-        sign = inv < F(0)
-        lo, hi = np.where(sign, sc.bmax, sc.bmin), np.where(sign, sc.bmin, sc.bmax)
-        t0 = (lo[:, 0] - o[:, 0]) * inv[:, 0]
-        t1 = (hi[:, 0] - o[:, 0]) * inv[:, 0]
-        ty0 = (lo[:, 1] - o[:, 1]) * inv[:, 1]
-        ty1 = (hi[:, 1] - o[:, 1]) * inv[:, 1]
-        ok = ~((t0 > ty1) | (ty0 > t1))
-        t0 = np.where(ty0 > t0, ty0, t0)
-        t1 = np.where(ty1 < t1, ty1, t1)
-        tz0 = (lo[:, 2] - o[:, 2]) * inv[:, 2]
-        tz1 = (hi[:, 2] - o[:, 2]) * inv[:, 2]
-        ok &= ~((t0 > tz1) | (tz0 > t1))
-        t0 = np.where(tz0 > t0, tz0, t0)
-        enter = np.where(inside, F(0), t0).astype(F)
-        g = np.where(inside[:, None], o, o + d * enter[:, None]).astype(F)
+        inside, ok, enter, g = box_entry(sc, o, d)
 
         # ---- grid.cpp:187-216: per-axis setup
         pos = np.clip(cvt_i32((g - sc.bmin) * sc.icw), 0, sc.dims - 1)    # ToVoxel
@@ -144,27 +153,48 @@ def walk(sc, rays, tminmax=None, mode="closest"):
             voxel[act] = cell
             kb = sc.offs[cell]
             ln = sc.offs[cell + 1] - kb
-            # ---- grid.cpp:243-267: the cell's list, position by position
+            # ---- grid.cpp:243-267: the cells' lists as one array of (ray, list position) pairs, a slice of rays at
+            # a time.  The list is tested in order, so a closest walk keeps the FIRST position that holds the least
+            # accepted cur_t (the strict "cur_t < t" never replaces an equal one), and an any-hit walk stops at the
+            # first counted position.
             best = np.full(act.size, FLT_MAX, F)             # closest: t (FLT_MAX at every cell's start)
             done = np.zeros(act.size, bool)                  # any: a test counted
-            live = np.flatnonzero(ln > 0)
-            k = 0
-            while live.size:
-                r = act[live]
-                ti = sc.cell_tris[kb[live] + k]
+            csum = np.cumsum(ln)
+            lo_row = 0
+            while lo_row < act.size:
+                base = int(csum[lo_row - 1]) if lo_row else 0
+                hi_row = max(lo_row + 1, int(np.searchsorted(csum, base + PAIRS_PER_SLICE, side="right")))
+                rows_of = np.arange(lo_row, hi_row)
+                lo_row = hi_row
+                sl = ln[rows_of]
+                m = int(sl.sum())
+                if m == 0:
+                    continue
+                first_pair = np.cumsum(sl) - sl
+                rows = np.repeat(rows_of, sl)
+                k = np.arange(m) - np.repeat(first_pair, sl)
+                seg = first_pair[sl > 0]                     # reduceat boundaries: the non-empty lists
+                srow = rows_of[sl > 0]
+                r = act[rows]
+                ti = sc.cell_tris[kb[rows] + k]
                 h, ct, cu, cv = ray_tri(o[r], d[r], sc.v0[ti], sc.v1[ti], sc.v2[ti])
-                tests[r] += 1
                 if anyhit:
-                    cnt = h & (ct < nax[live]) & (tmin[r] < ct) & (ct < tmax[r])
-                    done[live[cnt]] = True
-                    live = live[~cnt]
+                    cnt = h & (ct < nax[rows]) & (tmin[r] < ct) & (ct < tmax[r])
+                    first = np.minimum.reduceat(np.where(cnt, k, m), seg)
+                    found = first < m
+                    done[srow[found]] = True
+                    tests[act[srow]] += np.where(found, first + 1, sl[sl > 0]).astype(np.uint32)
                 else:
-                    take = h & (ct < best[live]) & (ct < nax[live])
-                    w, rw = live[take], r[take]
-                    best[w] = ct[take]
-                    tt[rw], uu[rw], vv[rw], tri[rw] = ct[take], cu[take], cv[take], ti[take]
-                k += 1
-                live = live[ln[live] > k]
+                    ok_t = h & (ct < FLT_MAX) & (ct < nax[rows])
+                    val = np.where(ok_t, ct, F(np.inf)).astype(F)
+                    least = np.minimum.reduceat(val, seg)
+                    found = least < F(np.inf)
+                    at = np.minimum.reduceat(np.where(ok_t & (val == np.repeat(least, sl[sl > 0])), np.arange(m), m), seg)
+                    w, at = srow[found], at[found]
+                    best[w] = ct[at]
+                    rw = act[w]
+                    tt[rw], uu[rw], vv[rw], tri[rw] = ct[at], cu[at], cv[at], ti[at]
+                    tests[act[srow]] += sl[sl > 0].astype(np.uint32)
             if anyhit:
                 hit[act[done]] = True
                 go = ~done & ~(nax >= tmax[act])             # rule 3

@@ -385,7 +385,9 @@ def off_camera_rays(rays, rec, lo, hi):
 def test_arms_agree_off_camera(scenes, name):
     """The fast arm's tri, t, u, v equal the counting arm's, bit for bit, on rays no camera makes; the set must
     hold at least 1,000 hits and 1,000 misses (by the counting arm).  RT_RAYS_SORT gives the same bits on the
-    same rays, with either arm."""
+    same rays, with either arm.  Both arms are grid_intersect over one dda_setup, so this says nothing about a
+    mistake they share: tests/test_gpu_ray_sets.py holds both to the reference's own Grid::Intersect on
+    off-camera rays (tests/golden/rays)."""
     import torch
     e = META["cases"][name]
     hs, gs = scenes(e)
