@@ -29,9 +29,13 @@
 //   alt-samples <scene.rtscene> W H spp x0 y0 w h brute|march <out.bin>
 //                                            records of Renderer::IntersectBruteForce / RayMarch
 //   render ... [--isect grid|brute|march]   the frame with another intersector (renderer.cpp:103-105)
-//   rays <scene.rtscene> <rays.f32> <out.rec>   Grid::Intersect on caller-supplied rays: in n x 6 f32 (origin,
-//                                            direction as passed), out n x 8 words hit, tri, t, u, v, voxel,
-//                                            steps, tests (the last three 0 in the uninstrumented build)
+//   rays <scene.rtscene> <rays.f32> <out.rec> [res]   Grid::Intersect on caller-supplied rays: in n x 6 f32
+//                                            (origin, direction as passed), out n x 8 words hit, tri, t, u, v,
+//                                            voxel, steps, tests (the last three 0 in the uninstrumented build);
+//                                            res: the grid's resolution, as for `grid` (default 64)
+//   tri <in.f32> <out.rec>                   IntersectRayTri (triangle.h:15-107) on caller-supplied pairs: in n x 15
+//                                            f32 (o, d, v0, v1, v2), out n x 4 words hit, t, u, v (t, u, v as the
+//                                            function left them, NaN-initialised, whatever it returned)
 //   kat <outdir>                             primitive known-answer vectors
 //   kat-dist <out.f32>                       DistancePointTri known answers
 
@@ -522,7 +526,7 @@ bool WriteFile(const char *path, const void *data, size_t bytes)
 
 int Usage()
 {
-    std::fprintf(stderr, "usage: refdriver dump-scenes|grid|render|samples|rays|kat ...\n");
+    std::fprintf(stderr, "usage: refdriver dump-scenes|grid|render|samples|rays [res]|tri|kat ...\n");
     return 2;
 }
 
@@ -835,14 +839,37 @@ int main(int argc, char **argv)
     if (cmd == "kat-dist" && argc == 3)
         return CmdKatDist(argv[2]);
 
+    if (cmd == "tri" && argc == 4)
+    {
+        struct TriRec { uint32 hit; float t, u, v; };
+        std::FILE *rf = std::fopen(argv[2], "rb");
+        if (!rf) { std::fprintf(stderr, "bad pair file\n"); return 1; }
+        std::vector<TriRec> recs;
+        float in[15];
+        while (std::fread(in, 4, 15, rf) == 15)
+        {
+            const float nan = std::numeric_limits<float>::quiet_NaN();
+            TriRec r;
+            r.t = r.u = r.v = nan;
+            r.hit = IntersectRayTri(Vec3f(in[0], in[1], in[2]), Vec3f(in[3], in[4], in[5]), Vec3f(in[6], in[7], in[8]),
+                                    Vec3f(in[9], in[10], in[11]), Vec3f(in[12], in[13], in[14]), r.t, r.u, r.v);
+            recs.push_back(r);
+        }
+        std::fclose(rf);
+        if (!WriteFile(argv[3], recs.empty() ? nullptr : &recs[0], recs.size() * sizeof(TriRec))) return 1;
+        std::printf("RESULT {\"tri\": %zu}\n", recs.size());
+        return 0;
+    }
+
     if ((cmd == "grid" && (argc == 4 || argc == 5)) || (cmd == "render" && argc >= 6) ||
-        (cmd == "samples" && argc >= 11) || (cmd == "alt-samples" && argc == 12) || (cmd == "rays" && argc == 5))
+        (cmd == "samples" && argc >= 11) || (cmd == "alt-samples" && argc == 12) || (cmd == "rays" && (argc == 5 || argc == 6)))
     {
         SceneFile sf;
         if (!ReadScene(argv[2], sf)) { std::fprintf(stderr, "bad scene file\n"); return 1; }
         const Mesh *mesh_ptr = sf.mesh.get();
-        // scene.cpp:6-7 builds with 64; "grid" takes another resolution (Grid::Grid's own parameter)
-        const uint grid_res = (cmd == "grid" && argc == 5) ? uint(std::atoi(argv[4])) : 64u;
+        // scene.cpp:6-7 builds with 64; "grid" and "rays" take another resolution (Grid::Grid's own parameter)
+        const uint grid_res = (cmd == "grid" && argc == 5) ? uint(std::atoi(argv[4]))
+                            : (cmd == "rays" && argc == 6) ? uint(std::atoi(argv[5])) : 64u;
         if (grid_res == 0) return Usage();
         const double tb0 = TimerGetTick();
         GridExport grid(std::move(sf.mesh), grid_res);

@@ -40,6 +40,9 @@ F = np.float32
 RAYS = os.path.join(GOLD, "rays")
 SEED = 20261020
 SCENES = ("inside", "stack1500", "stack2100", "negative_octant", "flat_front", "scene1", "scene8")
+# the scenes of tests/ray_variant_scenes.py (tests/golden/ray_variants): the same families, seeded by indices of
+# their own after SCENES', so the seven sets above keep their seeds
+VARIANT_SCENES = ("ribbon_x513", "ribbon_y513", "ribbon_z513", "ribbon_z512", "sheets16", "huge_axis_z", "huge_stack2100")
 THIN_SCENE = "flat_front"                     # 64 x 64 x 1 cells
 FAMILIES = (("A", 512), ("B", 384), ("C", 384), ("D", 256), ("E", 384), ("F", 192), ("G", 432), ("H", 200))
 NAMES = tuple(n for n, _ in FAMILIES)
@@ -175,7 +178,7 @@ class Box:
 
 
 def rng(scene, fam):
-    return np.random.Generator(np.random.PCG64([SEED, SCENES.index(scene), NAMES.index(fam)]))
+    return np.random.Generator(np.random.PCG64([SEED, (SCENES + VARIANT_SCENES).index(scene), NAMES.index(fam)]))
 
 
 def unit_dirs(r, n):

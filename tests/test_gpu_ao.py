@@ -73,16 +73,43 @@ def raw_ao(torch, gs, f, K, tmin, tmax, dirs=None, rotate=True, want_counts=True
     return b[:W * H].reshape(H, W).copy(), c
 
 
+class AoScene:
+    """One scene of these tests: .name, .hs (what rtm.GpuScene was made from: a HostScene, or a caller-built
+    description), .gs, .sc (the RefScene over the same arrays); it unpacks as (hs, gs, sc).  traced(W, H, spp): the
+    frame's camera rays and their closest hits from the library (host copies), computed once per frame shape."""
+
+    def __init__(self, name, hs, gs, sc):
+        self.name, self.hs, self.gs, self.sc = name, hs, gs, sc
+        self._traced = {}
+
+    def __iter__(self):
+        return iter((self.hs, self.gs, self.sc))
+
+    def __getitem__(self, i):
+        return (self.hs, self.gs, self.sc)[i]
+
+    def traced(self, W, H, spp):
+        import torch
+        key = (W, H, spp)
+        if key not in self._traced:
+            d_rays = self.gs.primary_rays(self.gs.frame(W, H, spp))
+            res = self.gs.trace_rays(d_rays)
+            torch.cuda.synchronize()
+            h = res.hits.cpu().numpy().view(np.uint32)
+            self._traced[key] = (d_rays.cpu().numpy(), h[:, 0].copy(), h[:, 1].view(np.float32).copy())
+        return self._traced[key]
+
+
 @pytest.fixture(scope="module")
 def scenes(tmp_path_factory):
-    """Per scene file: (HostScene, GpuScene, RefScene), loaded once."""
+    """Per scene file: an AoScene (HostScene, GpuScene, RefScene), loaded once."""
     tmp = tmp_path_factory.mktemp("ao")
     cache = {}
 
     def get(name):
         if name not in cache:
             hs = rtm.HostScene.load(S.scene_file({"scene": name}, tmp))
-            cache[name] = (hs, rtm.GpuScene(hs, 0), R.RefScene.from_host(hs))
+            cache[name] = AoScene(name, hs, rtm.GpuScene(hs, 0), R.RefScene.from_host(hs))
         return cache[name]
     yield get
     for hs, gs, _ in cache.values():
@@ -90,29 +117,10 @@ def scenes(tmp_path_factory):
         hs.close()
 
 
-@pytest.fixture(scope="module")
-def traced(scenes):
-    """Per (scene, W, H, spp): the camera rays and their closest hits from the library (host copies), computed once."""
-    import torch
-    cache = {}
-
-    def get(name, W, H, spp):
-        key = (name, W, H, spp)
-        if key not in cache:
-            hs, gs, sc = scenes(name)
-            d_rays = gs.primary_rays(gs.frame(W, H, spp))
-            res = gs.trace_rays(d_rays)
-            torch.cuda.synchronize()
-            h = res.hits.cpu().numpy().view(np.uint32)
-            cache[key] = (d_rays.cpu().numpy(), h[:, 0].copy(), h[:, 1].view(np.float32).copy())
-        return cache[key]
-    return get
-
-
-def composed(torch, scenes, traced, name, W, H, spp, dirs, rotate, tmin, tmax):
-    """The expected result: the composition of the three library calls and the restatement."""
-    hs, gs, sc = scenes(name)
-    rays, tri, t = traced(name, W, H, spp)
+def composed(torch, scene, W, H, spp, dirs, rotate, tmin, tmax):
+    """The expected result on an AoScene: the composition of the three library calls and the restatement."""
+    hs, gs, sc = scene
+    rays, tri, t = scene.traced(W, H, spp)
     f = A.form(sc, rays, tri, t, dirs, rtm.ao_rotations() if rotate else None, W, H, spp)
     m = f["ao_rays"].shape[0]
     occ = np.zeros(0, np.uint8)
@@ -126,10 +134,11 @@ def composed(torch, scenes, traced, name, W, H, spp, dirs, rotate, tmin, tmax):
     return A.pixels(cnt, K, W, H, spp), cnt.reshape(H, W, spp), f, occ
 
 
-def check(torch, scenes, traced, name, W, H, spp, K, rotate, tmin, tmax, dirs=None, what=""):
-    hs, gs, sc = scenes(name)
+def check(torch, scene, W, H, spp, K, rotate, tmin, tmax, dirs=None, what=""):
+    hs, gs, sc = scene
+    name = scene.name
     table = np.ascontiguousarray(dirs, np.float32) if dirs is not None else rtm.ao_table(K)
-    want_pix, want_cnt, f, occ = composed(torch, scenes, traced, name, W, H, spp, table, rotate, tmin, tmax)
+    want_pix, want_cnt, f, occ = composed(torch, scene, W, H, spp, table, rotate, tmin, tmax)
     got_pix, got_cnt = raw_ao(torch, gs, gs.frame(W, H, spp), table.shape[0], tmin, tmax, dirs=dirs, rotate=rotate)
     label = f"{name} {W}x{H}x{spp} K={table.shape[0]} rotate={rotate} ({float(tmin):g}, {float(tmax):g}) {what}"
     print(f"{label}: {int(f['hit'].sum())} hit samples, {int(occ.sum())} of {occ.size} AO rays occluded, "
@@ -145,7 +154,7 @@ def check(torch, scenes, traced, name, W, H, spp, K, rotate, tmin, tmax, dirs=No
 
 # ------------------------------------------------------------------ 1. views
 @pytest.mark.parametrize("name", VIEWS + EXTRA_VIEWS + tuple(SCENE_VIEWS))
-def test_views(scenes, traced, name):
+def test_views(scenes, name):
     """Every view at K = 4, rotated, tmin = 1e-4 x the diagonal, tmax = 0.25 x the diagonal (the setting
     tests/test_ao_cpu.py shows to be non-vacuous), and at K = 5 unrotated over (0, +inf).  stack2100 walks the plain
     CSR ranges, the others the box runs; on the stacks the any-hit rays run lists of 1,500 and 2,100 records."""
@@ -153,12 +162,12 @@ def test_views(scenes, traced, name):
     W, H, spp = SCENE_VIEWS[name] if name in SCENE_VIEWS else (META["cases"][name][k] for k in ("W", "H", "spp"))
     hs, gs, sc = scenes(name)
     d = sc.diagonal()
-    f, occ = check(torch, scenes, traced, name, W, H, spp, 4, True, np.float32(1e-4) * d, np.float32(0.25) * d)
+    f, occ = check(torch, scenes(name), W, H, spp, 4, True, np.float32(1e-4) * d, np.float32(0.25) * d)
     if name == "away":
         assert occ.size == 0
     elif name not in EXTRA_VIEWS:
         assert 0.02 <= float(occ.mean()) <= 0.98
-    check(torch, scenes, traced, name, W, H, spp, 5, False, np.float32(0), INF)
+    check(torch, scenes(name), W, H, spp, 5, False, np.float32(0), INF)
     assert gs.info()["packed_cells"] == (0 if name == "stack2100" else 1)
 
 
@@ -171,18 +180,18 @@ PARAMS = [  # K, spp, rotate, tmax / diagonal (None: +inf), tmin / diagonal
 
 
 @pytest.mark.parametrize("K,spp,rotate,tmax,tmin", PARAMS)
-def test_parameters(scenes, traced, K, spp, rotate, tmax, tmin):
+def test_parameters(scenes, K, spp, rotate, tmax, tmin):
     """K in {1, 4, 5, 16, 64} x spp in {1, 4, 16}, rotation on and off, tmax in {0.05, 0.25} x the diagonal and +inf,
     tmin in {0, 1e-4 x the diagonal}: `inside` at 33x21 (partial tiles; at spp 16 a tile is 64 waves)."""
     import torch
     d = scenes("inside")[2].diagonal()
-    f, occ = check(torch, scenes, traced, "inside", 33, 21, spp, K, rotate, np.float32(tmin) * d,
+    f, occ = check(torch, scenes("inside"), 33, 21, spp, K, rotate, np.float32(tmin) * d,
                    INF if tmax is None else np.float32(tmax) * d)
     assert 0 < int(occ.sum()) < occ.size
 
 
 @pytest.mark.parametrize("name", ["inside", "scene1"])
-def test_caller_directions_of_mixed_lengths(scenes, traced, name):
+def test_caller_directions_of_mixed_lengths(scenes, name):
     """A caller's table whose entries are the built-in directions scaled to lengths 0.5, 7.9 and 8.5 in turn (K = 6),
     used as passed: waves vote for the Newton reciprocal (|w|_inf <= 8) and for the division, some split.  t is in
     units of |w|, so the interval is what it is: no rescaling."""
@@ -191,7 +200,7 @@ def test_caller_directions_of_mixed_lengths(scenes, traced, name):
     dirs = (rtm.ao_table(6) * np.array([0.5, 7.9, 8.5, 8.5, 0.5, 7.9], np.float32)[:, None]).astype(np.float32)
     W, H, spp = (62, 46, 4) if name == "inside" else SCENE_VIEWS[name]
     for rotate in (True, False):
-        f, occ = check(torch, scenes, traced, name, W, H, spp, 6, rotate, np.float32(1e-4) * d, np.float32(0.25) * d, dirs=dirs,
+        f, occ = check(torch, scenes(name), W, H, spp, 6, rotate, np.float32(1e-4) * d, np.float32(0.25) * d, dirs=dirs,
                        what="caller dirs")
         wm = np.abs(f["w"]).max(2)
         assert (wm > 8).any() and (wm <= 8).any() and (wm[:, 2] > 8).any() and (wm[:, 3] <= 8).any()
@@ -201,15 +210,15 @@ def test_caller_directions_of_mixed_lengths(scenes, traced, name):
 # ------------------------------------------------------------------ 3. frame shapes
 @pytest.mark.parametrize("W,H,spp", [(1, 1, 4), (15, 17, 4), (16, 16, 4), (17, 1, 4), (63, 47, 4), (130, 3, 4), (3, 3, 64),
                                      (17, 16, 1), (16, 17, 2), (5, 3, 32), (9, 2, 8)])
-def test_frame_shapes(scenes, traced, W, H, spp):
+def test_frame_shapes(scenes, W, H, spp):
     """Partial tiles, one-wave launches, every power-of-two spp; at spp 64 one pixel fills a wave."""
     import torch
     d = scenes("inside")[2].diagonal()
-    check(torch, scenes, traced, "inside", W, H, spp, 4, True, np.float32(1e-4) * d, np.float32(0.25) * d)
+    check(torch, scenes("inside"), W, H, spp, 4, True, np.float32(1e-4) * d, np.float32(0.25) * d)
 
 
 # ------------------------------------------------------------------ 5. launch sequences
-def test_ao_frame_between_render_frames_on_other_streams(scenes, traced, golden):
+def test_ao_frame_between_render_frames_on_other_streams(scenes, golden):
     """render_frame_device, an AO frame and render_frame_device again, of one scene on three streams without a host
     wait (1920x1080x4 frames of scene 8, whose tables the 96x54x4 AO frame rewrites and the second frame rewrites
     back): both frames have the golden SHA, the AO frame the bytes of the composition."""
@@ -221,7 +230,7 @@ def test_ao_frame_between_render_frames_on_other_streams(scenes, traced, golden)
     W, H, spp = SCENE_VIEWS[name]
     d = sc.diagonal()
     tmin, tmax = np.float32(1e-4) * d, np.float32(0.25) * d
-    want_pix, want_cnt, f, occ = composed(torch, scenes, traced, name, W, H, spp, rtm.ao_table(4), True, tmin, tmax)
+    want_pix, want_cnt, f, occ = composed(torch, scenes(name), W, H, spp, rtm.ao_table(4), True, tmin, tmax)
     big = gs.frame(1920, 1080, 4)
     outs = [torch.full((1920 * 1080,), S.SENTINEL, dtype=torch.int32, device="cuda") for _ in range(2)]
     s0, s1, s2 = torch.cuda.Stream(), torch.cuda.Stream(), torch.cuda.Stream()
@@ -244,7 +253,7 @@ def test_ao_frame_between_render_frames_on_other_streams(scenes, traced, golden)
     np.testing.assert_array_equal(b[:W * H].reshape(H, W), want_pix)
 
 
-def test_graph_capture_and_replay(scenes, traced):
+def test_graph_capture_and_replay(scenes):
     """One warm-up call of the frame, the call captured in a graph (torch.cuda.CUDAGraph), two replays into cleared
     buffers: the composition's bytes each time.  A caller's table is read during the captured call only."""
     import torch
@@ -254,7 +263,7 @@ def test_graph_capture_and_replay(scenes, traced):
     d = sc.diagonal()
     tmin, tmax = np.float32(1e-4) * d, np.float32(0.25) * d
     dirs = np.ascontiguousarray(rtm.ao_table(5)[::-1])
-    want_pix, want_cnt, f, occ = composed(torch, scenes, traced, name, W, H, spp, dirs, True, tmin, tmax)
+    want_pix, want_cnt, f, occ = composed(torch, scenes(name), W, H, spp, dirs, True, tmin, tmax)
     bgra = torch.full((W * H + TAIL,), S.SENTINEL, dtype=torch.int32, device="cuda")
     cnt = torch.full((W * H * spp + TAIL,), FILL, dtype=torch.uint8, device="cuda")
     p, keep = ao_struct(5, tmin, tmax, dirs.copy(), True)
@@ -279,7 +288,7 @@ def test_graph_capture_and_replay(scenes, traced):
         np.testing.assert_array_equal(b[:W * H].reshape(H, W), want_pix)
 
 
-def test_python_surface(scenes, traced):
+def test_python_surface(scenes):
     """GpuScene.render_ao: a torch.uint32 [H, W] tensor (and uint8 [H, W, spp] counts), in place with out=, on another
     stream; the raw call's bytes."""
     import torch

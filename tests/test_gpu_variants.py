@@ -26,7 +26,6 @@ Where the grid is the reference's (resolution 64), the live CPU restatement is c
 64x64x4 frames with test_gpu_uniform_lists.OFFSETS: pixel (32, 32) sample 0 looks exactly down the camera axis.
 One test per case, so that a fault can be attributed to one case.
 """
-import ctypes
 import os
 
 import numpy as np
@@ -34,6 +33,7 @@ import pytest
 
 import synth_scenes as S
 from conftest import load_package, nan_equal_bits
+from ray_variant_scenes import CallerBuilt
 from test_gpu_uniform_lists import H, OFFSETS, REC_WORDS, SHARED_WORDS, SPP, W, check_against_plain_walk
 
 pytestmark = pytest.mark.gpu
@@ -258,54 +258,6 @@ def test_b4_no_octant_words():
 
 
 # ------------------------------------------------------------------ B5
-class CallerBuilt:
-    """A caller-built rt_scene_desc, which rt_scene_create accepts (it validates indices and offsets only):
-    a host scene's arrays plus one triangle with edges of 2^62, listed by hand at the end of some cells' lists.
-    Has what GpuScene and VScene use of a HostScene: desc(), cam, fov, save()."""
-
-    def __init__(self, hs, layer=20, lo=20, hi=45):
-        v, t = hs.mesh()
-        g, offs, refs = hs.grid()
-        self.g = g
-        nv, nt = v.shape[0], t.shape[0]
-        z = np.float32(g["aabb_min"][2] + np.float32(layer + 0.5) * g["cell_wdh"])
-        big = np.float32(2.0 ** 61)
-        # e1 = (2^62, 0, 0), e2 = (2^61, 2^62, 0): |e1|_1 |e2|_1 = 1.5 * 2^124 >= 2^120; the plane z = const
-        # crosses every listed cell, behind the scene's own triangles as the -z cameras see them
-        pts = np.array([[-big, -big, z], [big, -big, z], [0.0, big, z]], np.float32)
-        ev = np.zeros((3, 6), np.float32)
-        ev[:, :3], ev[:, 5] = pts, 1.0
-        et = np.zeros((1, 6), np.uint32)
-        et[0, :3] = (nv, nv + 1, nv + 2)
-        et[0, 5] = np.float32(1.0).view(np.uint32)
-        self.v = np.ascontiguousarray(np.concatenate([v, ev]))
-        self.t = np.ascontiguousarray(np.concatenate([t, et]))
-        dx, dy, dz = g["dims"]
-        xs, ys = np.meshgrid(np.arange(lo, hi), np.arange(lo, hi))
-        cells = np.sort((xs + layer * dx + ys * dx * dz).reshape(-1)).astype(np.int64)        # grid.h:41-42
-        add = np.zeros(offs.size - 1, np.int64)
-        add[cells] = 1
-        self.refs = np.ascontiguousarray(np.insert(refs, offs[cells + 1].astype(np.int64), nt).astype(np.uint32))
-        self.offs = np.ascontiguousarray(np.concatenate([[0], np.cumsum(np.diff(offs.astype(np.int64)) + add)])
-                                         .astype(np.uint32))
-        self.listed = cells.size
-        self.cam, self.fov = hs.cam.copy(), hs.fov
-
-    def desc(self):
-        d = rtm.SceneDesc()
-        d.num_vertices, d.num_triangles = self.v.shape[0], self.t.shape[0]
-        d.vertices = self.v.ctypes.data_as(ctypes.POINTER(rtm.Vertex))
-        d.triangles = self.t.ctypes.data_as(ctypes.POINTER(rtm.Triangle))
-        for a in range(3):
-            d.grid.dims[a] = int(self.g["dims"][a])
-            d.grid.aabb_min[a] = float(self.g["aabb_min"][a])
-            d.grid.aabb_max[a] = float(self.g["aabb_max"][a])
-        d.grid.cell_wdh, d.grid.inv_cell_wdh = float(self.g["cell_wdh"]), float(self.g["inv_cell_wdh"])
-        d.grid.cell_offsets = self.offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
-        d.grid.cell_tris = self.refs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
-        return d
-
-
 def test_b5_not_rcp_safe():
     """The sparse scene plus a triangle with |e1|_1 |e2|_1 = 1.5 * 2^124: rcp_safe == 0 with box words and
     pack_ok, i.e. kVarAutoCore | kVarPackedRem | kVarSkipRun (the exact reciprocal inside the box-run walk)."""
