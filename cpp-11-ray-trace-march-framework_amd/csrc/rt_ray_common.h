@@ -1,6 +1,7 @@
 // rt_ray_common.h -- what the ray-query translation units share (rt_rays.hip: rt_trace_rays_device;
 // rt_occlusion.hip: rt_occluded_rays_device; rt_ao.hip: rt_render_ao_device) beside rt_walk.h's walk.
 #pragma once
+#include "rt_cam_bound.h"
 #include "rt_walk.h"
 
 namespace rtk {
@@ -15,10 +16,16 @@ __device__ __forceinline__ bool finite_f32(float x)
 
 // kVarFastRcp for rays: rt_scene::rcp_safe bounds |e1|_1 |e2|_1 below 2^120, which keeps
 // |det| = |e1 . (d x e2)| <= 2 |d|_inf |e1|_1 |e2|_1 inside rcp_nr's exact range (< 2^126) for a
-// direction of |d|_inf <= kRcpMaxDir with a factor of 4 to spare for the roundings; the camera's unit
-// directions are far inside.  d is used as the caller passes it, so a wave that holds a longer direction
-// takes the same walk with the correctly rounded division instead (a wave-uniform choice: same bits).
+// direction of |d|_inf <= kRcpMaxDir with a factor of 4 to spare for the roundings.  d is used as the caller
+// passes it, so a wave that holds a longer direction takes the same walk with the correctly rounded division
+// instead (a wave-uniform choice: same bits).
+// The render kernels take no such vote.  Their directions are the frame's camera rays, whose length is whatever
+// rt_frame.cam's 3x3 makes it (the direction is normalised before the matrix, rtd::dir_from_xy): an
+// orthonormal camera's are far inside, and for any other the host bounds |d|_inf per frame from the matrix
+// (rt_cam_bound.h) and launches the instantiation without kVarFastRcp when the bound exceeds kRcpMaxDir
+// (rt_tracer.hip, frame_traversal_bits).
 constexpr float kRcpMaxDir = 8.0f;
+static_assert(double(kRcpMaxDir) == kCamRcpMaxDir, "rt_cam_bound.h bounds camera directions against kRcpMaxDir");
 
 // RT_RAYS_SORT: a ray's sort word is index << kKeyBits | key (rt_rays.hip, k_ray_keys)
 constexpr uint32_t kKeyBits = 32;

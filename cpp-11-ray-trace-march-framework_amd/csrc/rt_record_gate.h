@@ -9,7 +9,10 @@
 //
 // ---- derivation ------------------------------------------------------------------------------------
 // One CSR reference with f32 e1, e2, T = o - v0 (as rtd::make_frec forms them) and an f32 ray direction
-// D with |D_i| <= Dmax = 1.0001 (GenerateRay normalises it).  u = 2^-24, fl() = one f32 rounding,
+// D with |D_i| <= Dmax = 1.0001.  GenerateRay normalises the camera-space direction and multiplies by the
+// camera's 3x3 AFTERWARDS, so this holds for an orthonormal camera and not for any rt_frame.cam: the host
+// bounds |D_i| per frame from the matrix (rt_cam_bound.h) and passes the gate records only to frames inside
+// Dmax (rt_tracer.hip, frame_gated); the others take the ungated loop.  u = 2^-24, fl() = one f32 rounding,
 // g_k = k u / (1 - k u).  The reference computes (rtd::mt_rec_first, the order of triangle.h:45-87)
 //     p     = fl(D x e2)                          each component fl(fl(a b) - fl(c d))
 //     det_r = fl(fl(fl(e1x px) + fl(e1y py)) + fl(e1z pz)),   y_r likewise with T for e1
@@ -67,7 +70,7 @@ namespace rtk {
 // One gate record: 8 floats (32 B) per CSR reference, as (nz_i, nh_i) pairs for packed f32 math:
 //   { nz.x, nh.x, nz.y, nh.y, nz.z, nh.z, E, 0 }
 constexpr uint32_t kGateFloats = 8;
-constexpr double kGateDmax = 1.0001;            // bound of a ray direction's components
+constexpr double kGateDmax = 1.0001;            // bound of a ray direction's components (rt_cam_bound.h checks it)
 constexpr double kGateU = 1.0 / 16777216.0;     // 2^-24
 constexpr double kGateMaxIn = 1099511627776.0;  // 2^40
 

@@ -39,6 +39,7 @@
 #include "rt_device.h"
 #include "rt_internal.h"
 #include "rt_box_words.h"
+#include "rt_cam_bound.h"
 #include "rt_scene.h"
 
 using namespace rtk;
@@ -162,6 +163,24 @@ bool auto_runs(const rt_scene *s)
 int scene_traversal_bits(const rt_scene *s)
 {
     return (s->rcp_safe ? kVarFastRcp : 0) | (auto_runs(s) ? kVarPackedRem | kVarSkipRun : 0);
+}
+
+// The same for one frame of a render launch: rt_frame.cam's 3x3 need not be orthonormal, and the direction is
+// normalised BEFORE it (rtd::dir_from_xy), so the frame's directions are as long as the matrix makes them.
+// kVarFastRcp's proof holds up to |d|_inf = kRcpMaxDir (rt_ray_common.h); a frame whose bound (rt_cam_bound.h,
+// fp64, from the 3x3 alone) is above that or not finite takes the instantiation without the bit, the one a
+// scene with rcp_safe = 0 takes.  The render kernels hold no per-wave vote for this: the choice is per frame.
+int frame_traversal_bits(const rt_scene *s, const KParams& P)
+{
+    const int v = scene_traversal_bits(s);
+    return cam_fast_rcp_ok(cam_dir_bound(P.m)) ? v : (v & ~kVarFastRcp);
+}
+
+// The record gate's per-record bound E is computed for |D_i| <= kGateDmax (rt_record_gate.h): a frame whose
+// bound is above that or not finite runs without gate records, the loop of a scene created with RT_REC_GATE=0.
+bool frame_gated(const rt_scene *s, const KParams& P)
+{
+    return s->rec_gate && cam_gate_ok(cam_dir_bound(P.m));
 }
 
 int ensure_device(const rt_scene *s)
@@ -479,7 +498,8 @@ bool fref_overlap_ok(const rt_scene *s, const float org[3])
 // launch per frame), ordered after every launch that may still read that buffer: the caller has ordered
 // st after the launch before the last one and -- unless this launch overlaps it, when its buffers count as
 // busy -- after the last one (order_all); busy: buffers that frames of this call read already.
-// Sets P.frefs (and P.gates, the buffer's gate array) and marks the buffer in *used.
+// Sets P.frefs (and P.gates, the buffer's gate array -- null for a frame whose camera is outside the gate's
+// proof, frame_gated) and marks the buffer in *used.
 int ensure_origin_terms(rt_scene *s, KParams& P, hipStream_t st, uint32_t busy, uint32_t *used)
 {
     bool compute = false;
@@ -497,7 +517,7 @@ int ensure_origin_terms(rt_scene *s, KParams& P, hipStream_t st, uint32_t busy, 
         rtk::fref_computed(s->fref, b, ob);
     }
     P.frefs = s->d_frefs[b];
-    P.gates = s->rec_gate ? s->d_gates[b] : nullptr;
+    P.gates = frame_gated(s, P) ? s->d_gates[b] : nullptr;
     *used |= 1u << b;
     return RT_OK;
 }
@@ -540,7 +560,7 @@ int launch_render(rt_scene *s, const rt_frame *f, KParams& P, uint32_t n_local_t
         !auto_wide(s, P) && P.spp <= 64u && !s->tab_dirty)
     {
         overlap = fref_overlap_ok(s, P.org);
-        const int v = kVarAutoCore | scene_traversal_bits(s);
+        const int v = kVarAutoCore | frame_traversal_bits(s, P);
         if (overlap && blocks >= s->hf_min_blocks)
         {
             const HfPeek pk = hf_peek(s, P, blocks, v, 0u, cam_signature(P));
@@ -568,7 +588,7 @@ int launch_render(rt_scene *s, const rt_frame *f, KParams& P, uint32_t n_local_t
     int var = 0;
     if (auto_path)
     {
-        var = kVarAutoCore | scene_traversal_bits(s) | ((f->kernel & RT_KERNEL_FLAG_WAVE_CLOCK) ? kVarWaveClock : 0);
+        var = kVarAutoCore | frame_traversal_bits(s, P) | ((f->kernel & RT_KERNEL_FLAG_WAVE_CLOCK) ? kVarWaveClock : 0);
         uint32_t used = 0;
         if (int rc = ensure_origin_terms(s, P, st, 0u, &used)) return rc;
         rtk::fref_launched(s->fref, used);
@@ -633,7 +653,7 @@ int launch_render(rt_scene *s, const rt_frame *f, KParams& P, uint32_t n_local_t
         RT_HIP(mark(kt0));
         // bary: the plain distance-skip walk; AUTO's box-run walk where the scene allows it
         const kcfn_t cfn = bary ? compact_kernel(RT_TRI_BARYCENTRIC, kVarDistSkip)
-                           : (auto_runs(s) && s->rcp_safe)
+                           : (auto_runs(s) && (var & kVarFastRcp))        // (rcp_safe, and this frame's camera)
                                ? compact_kernel(RT_TRI_MOLLER_TRUMBORE, kVarCompactBox)
                                : compact_kernel(RT_TRI_MOLLER_TRUMBORE, kVarWaveGate | kVarDistSkip | kVarOriginPre);
         hipLaunchKernelGGL(cfn, grid, wg, 0, st, P, n_items, refill);
@@ -771,8 +791,11 @@ int launch_batch(rt_scene *const *S, const rt_frame *F, uint32_t n, KParams *P, 
         if (P[i].isect != RT_ISECT_GRID || P[i].tri_test != RT_TRI_MOLLER_TRUMBORE) return RT_E_INVALID;
         if (P[i].W != P[0].W || P[i].H != P[0].H || P[i].spp != spp || S[i]->device != S[0]->device)
             return RT_E_INVALID;
-        const int v = kVarAutoCore | scene_traversal_bits(S[i]);
+        // (the frame's camera counts: rt_cam_bound.h; a frame whose gate or reciprocal choice differs from
+        // frame 0's cannot share the launch, and one without kVarFastRcp has no batch kernel)
+        const int v = kVarAutoCore | frame_traversal_bits(S[i], P[i]);
         if (var >= 0 && v != var) return RT_E_INVALID;
+        if (cam_gate_ok(cam_dir_bound(P[i].m)) != cam_gate_ok(cam_dir_bound(P[0].m))) return RT_E_INVALID;
         var = v;
         wide_heavy = wide_heavy || (F[i].kernel & RT_KERNEL_FLAG_WIDE_HEAVY) ||
                      (P[i].nranks >= 2u && S[i]->max_cell_refs >= S[0]->wh_auto_refs);

@@ -109,7 +109,10 @@ enum rt_kernel {
     RT_KERNEL_FLAG_EXHAUSTIVE = 0x8000, /* OR-able, ray march: evaluate every triangle per step
                                            (no block culling; A/B arm, identical results) */
     RT_KERNEL_FLAG_WAVE_CLOCK = 0x400000, /* OR-able (AUTO), debug: record s_memtime {start, end} of
-                                             every 64-sample work item (rt_debug_wave_clocks) */
+                                             every 64-sample work item (rt_debug_wave_clocks).  Built for AUTO's
+                                             full feature set only: on a scene without rcp_safe or packed
+                                             cells, and on a frame whose camera bound exceeds 8 (rt_frame.cam),
+                                             the launch returns RT_E_INVALID ("kernel variant not built") */
     RT_KERNEL_FLAG_OVERLAP = 0x800000, /* OR-able (AUTO; in a batch: every frame of it): the caller
                                           lets this launch run beside the scene's previous launch when
                                           that one is on another stream (it writes other output
@@ -134,7 +137,19 @@ enum rt_kernel {
 /* Per-frame parameters: what Renderer::RenderTile reads from the Scene and itself. */
 typedef struct rt_frame {
     float        cam[16];         /* Matrix44f::m_mat row-major [4][4] (lin_alg.h:689), from
-                                     Scene::GetCameraParameters (scene.h:17-18) */
+                                     Scene::GetCameraParameters (scene.h:17-18).  The upper-left 3x3 need not be
+                                     orthonormal: GenerateRay normalises the camera-space direction first and
+                                     multiplies by the 3x3 afterwards, so a scaled, sheared, mirrored or singular
+                                     3x3 gives rays whose direction is as long as the matrix makes it, and every
+                                     frame is the reference's for that matrix.  Two shortcuts of RT_KERNEL_AUTO /
+                                     COMPACT are proven for (near-)unit directions only; the library bounds the
+                                     direction's components per frame from the 3x3 (largest column norm) and a
+                                     frame above 1.0001 runs without the record gate, one above 8 -- or with a
+                                     non-finite entry -- also without the Newton reciprocal, the wide section
+                                     and one-wave workgroups.  Such a frame does not share a batched launch with
+                                     frames that keep them (rt_scene_info.batch_fallbacks counts it).  Same
+                                     bits, somewhat slower.  The debug flag RT_KERNEL_FLAG_WAVE_CLOCK is
+                                     not available on a frame above 8 (RT_E_INVALID). */
     float        fov;             /* horizontal FOV in degrees (camera.h:39-45) */
     uint32_t     width, height;   /* Framebuffer m_width / m_height (framebuffer.h:29-30) */
     uint32_t     spp;             /* Renderer::m_sample_count (renderer.h:34); 0 -> 1 */

@@ -67,14 +67,14 @@ class CallerBuilt:
     a host scene's arrays plus one triangle with edges of 2^62, listed by hand at the end of some cells' lists.
     Has what GpuScene and VScene use of a HostScene: desc(), cam, fov, save()."""
 
-    def __init__(self, hs, layer=20, lo=20, hi=45):
+    def __init__(self, hs, layer=20, lo=20, hi=45, big=2.0 ** 61):
         v, t = hs.mesh()
         g, offs, refs = hs.grid()
         self.g = g
         nv, nt = v.shape[0], t.shape[0]
         z = np.float32(g["aabb_min"][2] + np.float32(layer + 0.5) * g["cell_wdh"])
-        big = np.float32(2.0 ** 61)
-        # e1 = (2^62, 0, 0), e2 = (2^61, 2^62, 0): |e1|_1 |e2|_1 = 1.5 * 2^124 >= 2^120; the plane z = const
+        big = np.float32(big)
+        # big = 2^61: e1 = (2^62, 0, 0), e2 = (2^61, 2^62, 0): |e1|_1 |e2|_1 = 1.5 * 2^124 >= 2^120; the plane z = const
         # crosses every listed cell, behind the scene's own triangles as the -z cameras see them
         pts = np.array([[-big, -big, z], [big, -big, z], [0.0, big, z]], np.float32)
         ev = np.zeros((3, 6), np.float32)

@@ -4,11 +4,22 @@
 //   g++ -O2 -std=c++17 -pthread -ffp-contract=off tests/record_gate_check.cpp -o record_gate_check
 //   record_gate_check scene data/scenes/scene8.rtscene 1920 1080 4 16     every 16th tile of the frame
 //   record_gate_check adversarial 1 1000000                               seeded families, cases each
+//   record_gate_check adversarial 1 1000000 m0 .. m8      ... every direction through the camera's 3x3 first
+//   record_gate_check scene FILE W H spp stride [min_list] [--cam c0 .. c15] [--fov deg] [--grid-res n]
+//                                               [--offsets x0 y0 ..]     another view, grid, sample table
+//   record_gate_check bound m0 .. m8            rtk::cam_dir_bound of a 3x3 and what the library does with it
+// rt_frame.cam's 3x3 need not be orthonormal: the direction is normalised first and multiplied by the matrix
+// afterwards (rtd::dir_from_xy), so a scaled matrix gives directions the gate's bound E was not computed for.
+// csrc/rt_cam_bound.h (the function the library calls per frame) says which matrices keep the gate; the
+// checker shows that the gate is sound for those and is NOT for others (why the library's fall-back exists).
 // Soundness: no (ray, record) pair with ok1 true and the gate rejecting.  Selectivity (scene mode): how
 // often a wave's vote passes a record of a wave-uniform list, for ok1 and for the gate (waves as in
 // tools/wave_sim.cpp: 64 consecutive sample slots of a 16x16 tile in Morton order, in lock-step).
+// wholly_gated_ok1 (scene mode): records of wave-uniform lists of min_list or more that the gate vote skips
+// (every lane rejects) while some lane's ok1 holds -- each one a record the gated loop would wrongly skip.
 #include "../oracle/cpu_tracer.cpp"
 #include "../cpp-11-ray-trace-march-framework_amd/csrc/rt_record_gate.h"
+#include "../cpp-11-ray-trace-march-framework_amd/csrc/rt_cam_bound.h"
 
 #include <algorithm>
 #include <atomic>
@@ -123,23 +134,49 @@ struct Acc
     uint64_t lane_tests = 0, ok1_true = 0, gate_rejects = 0, violations = 0;
     uint64_t uni_recs = 0, uni_ok1 = 0, uni_gate = 0;           // uniform lists: records, wave votes passed
     uint64_t long_recs = 0, long_ok1 = 0, long_gate = 0;        // ... of lists of min_list records or more
+    uint64_t wholly_gated_ok1 = 0;                              // ... skipped by the vote though a lane's ok1 holds
     void add(const Acc& o)
     {
         lane_tests += o.lane_tests; ok1_true += o.ok1_true; gate_rejects += o.gate_rejects; violations += o.violations;
         uni_recs += o.uni_recs; uni_ok1 += o.uni_ok1; uni_gate += o.uni_gate;
         long_recs += o.long_recs; long_ok1 += o.long_ok1; long_gate += o.long_gate;
+        wholly_gated_ok1 += o.wholly_gated_ok1;
     }
 };
 
 int scene_mode(int argc, char **argv)
 {
-    if (argc < 7) { std::fprintf(stderr, "usage: record_gate_check scene file.rtscene W H spp tile_stride [min_list]\n"); return 2; }
+    if (argc < 7)
+    {
+        std::fprintf(stderr, "usage: record_gate_check scene file.rtscene W H spp tile_stride [min_list] [--cam c0 .. c15] "
+                             "[--fov deg] [--grid-res n] [--offsets x0 y0 ..]\n");
+        return 2;
+    }
     Scene s;
     if (!ReadScene(argv[2], s)) { std::fprintf(stderr, "cannot read %s\n", argv[2]); return 1; }
-    BuildGrid(s, 64);
     const uint32_t W = std::atoi(argv[3]), H = std::atoi(argv[4]), spp = std::atoi(argv[5]);
-    const uint32_t stride = std::max(1, std::atoi(argv[6])), min_list = argc > 7 ? std::atoi(argv[7]) : 8;
-    const std::vector<float> smp = Hammersley(spp);
+    const uint32_t stride = std::max(1, std::atoi(argv[6]));
+    uint32_t min_list = 8, grid_res = 64;
+    std::vector<float> smp = Hammersley(spp);
+    int ai = 7;
+    if (ai < argc && argv[ai][0] != '-') min_list = std::atoi(argv[ai++]);
+    while (ai < argc)
+    {
+        const std::string opt = argv[ai++];
+        const uint32_t need = opt == "--cam" ? 16u : (opt == "--offsets" ? 2u * spp : 1u);
+        if (uint32_t(argc - ai) < need) { std::fprintf(stderr, "%s takes %u values\n", opt.c_str(), need); return 2; }
+        if (opt == "--cam")
+            for (int k = 0; k < 16; k++) s.cam[k / 4][k % 4] = std::strtof(argv[ai++], nullptr);   // (hex floats too)
+        else if (opt == "--fov") s.fov = std::strtof(argv[ai++], nullptr);
+        else if (opt == "--grid-res") grid_res = std::atoi(argv[ai++]);
+        else if (opt == "--offsets")
+            for (uint32_t k = 0; k < 2u * spp; k++) smp[k] = std::strtof(argv[ai++], nullptr);
+        else { std::fprintf(stderr, "unknown option %s\n", opt.c_str()); return 2; }
+    }
+    BuildGrid(s, grid_res);
+    const float m9[9] = { s.cam[0][0], s.cam[0][1], s.cam[0][2], s.cam[1][0], s.cam[1][1], s.cam[1][2],
+                          s.cam[2][0], s.cam[2][1], s.cam[2][2] };
+    const double bound = rtk::cam_dir_bound(m9);
     const uint32_t tiles_x = (W + 15) / 16, tiles_y = (H + 15) / 16, items_per_tile = 256 * spp / 64;
     // every camera ray starts at the same origin (camera.h:43): the gate records of every reference
     V3 org, d0;
@@ -222,7 +259,11 @@ int scene_mode(int argc, char **argv)
                             any_ok1 |= p; any_pass |= !r;
                         }
                         a.uni_recs++; a.uni_ok1 += any_ok1; a.uni_gate += any_pass;
-                        if (L >= min_list) { a.long_recs++; a.long_ok1 += any_ok1; a.long_gate += any_pass; }
+                        if (L >= min_list)
+                        {
+                            a.long_recs++; a.long_ok1 += any_ok1; a.long_gate += any_pass;
+                            a.wholly_gated_ok1 += any_ok1 && !any_pass;
+                        }
                     }
                 }
             }
@@ -233,12 +274,14 @@ int scene_mode(int argc, char **argv)
     std::printf("{\"mode\": \"scene\", \"tiles\": %u, \"waves\": %u, \"min_list\": %u, \"one_origin\": %s,\n"
                 " \"lane_tests\": %llu, \"ok1_true\": %llu, \"gate_rejects\": %llu, \"violations\": %llu,\n"
                 " \"uniform_records\": %llu, \"uniform_ok1_votes\": %llu, \"uniform_gate_votes\": %llu,\n"
-                " \"long_records\": %llu, \"long_ok1_votes\": %llu, \"long_gate_votes\": %llu}\n",
+                " \"long_records\": %llu, \"long_ok1_votes\": %llu, \"long_gate_votes\": %llu,\n"
+                " \"wholly_gated_ok1\": %llu, \"cam_bound\": %.17g, \"gate_ok\": %s}\n",
                 uint32_t(tiles.size()), nitems, min_list, bad_origin ? "false" : "true",
                 (unsigned long long)a.lane_tests, (unsigned long long)a.ok1_true, (unsigned long long)a.gate_rejects,
                 (unsigned long long)a.violations, (unsigned long long)a.uni_recs, (unsigned long long)a.uni_ok1,
                 (unsigned long long)a.uni_gate, (unsigned long long)a.long_recs, (unsigned long long)a.long_ok1,
-                (unsigned long long)a.long_gate);
+                (unsigned long long)a.long_gate, (unsigned long long)a.wholly_gated_ok1, bound,
+                rtk::cam_gate_ok(bound) ? "true" : "false");
     return 0;
 }
 
@@ -268,10 +311,45 @@ struct Fam
 
 struct Case { V3 o, v0, v1, v2, d; };
 
+// the camera's 3x3 (adversarial mode's optional argument): applied to a normalised direction as rtd::dir_from_xy
+// applies it (Transf3x3, row-vector convention), or not at all.  Which normalised direction: the one the camera
+// would need for the ray to leave along the family's direction c.d -- c.d times the inverse matrix (fp64),
+// normalised as GenerateRay normalises -- so the family still aims where it means to, a few ulp off, whatever the
+// matrix rotates or scales; c.d itself for a singular matrix.
+bool g_have_m = false, g_have_inv = false;
+float g_m[9];
+double g_minv[9];
+
+void set_matrix(const float m[9])
+{
+    std::memcpy(g_m, m, sizeof(g_m));
+    g_have_m = true;
+    const double a[9] = { m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7], m[8] };
+    const double c[9] = { a[4] * a[8] - a[5] * a[7], a[2] * a[7] - a[1] * a[8], a[1] * a[5] - a[2] * a[4],
+                          a[5] * a[6] - a[3] * a[8], a[0] * a[8] - a[2] * a[6], a[2] * a[3] - a[0] * a[5],
+                          a[3] * a[7] - a[4] * a[6], a[1] * a[6] - a[0] * a[7], a[0] * a[4] - a[1] * a[3] };
+    const double det = a[0] * c[0] + a[1] * c[3] + a[2] * c[6];
+    const double scale = std::fabs(a[0]) + std::fabs(a[1]) + std::fabs(a[2]) + std::fabs(a[3]) + std::fabs(a[4]) +
+                         std::fabs(a[5]) + std::fabs(a[6]) + std::fabs(a[7]) + std::fabs(a[8]);
+    g_have_inv = std::isfinite(det) && std::fabs(det) > 1e-6 * scale * scale * scale;
+    for (int k = 0; g_have_inv && k < 9; k++) g_minv[k] = c[k] / det;
+}
+
 void run_case(Fam& f, const Case& c)
 {
     const Rec r = make_rec(c.o, c.v0, c.v1, c.v2);
-    const bool p = ok1(r, c.d.x, c.d.y, c.d.z), rej = gate(r, c.d.x, c.d.y, c.d.z);
+    V3 d = c.d;
+    if (g_have_m)
+    {
+        V3 p = c.d;
+        if (g_have_inv)
+            p = dir_of(double(c.d.x) * g_minv[0] + double(c.d.y) * g_minv[3] + double(c.d.z) * g_minv[6],
+                       double(c.d.x) * g_minv[1] + double(c.d.y) * g_minv[4] + double(c.d.z) * g_minv[7],
+                       double(c.d.x) * g_minv[2] + double(c.d.y) * g_minv[5] + double(c.d.z) * g_minv[8]);
+        d = mk(p.x * g_m[0] + p.y * g_m[3] + p.z * g_m[6], p.x * g_m[1] + p.y * g_m[4] + p.z * g_m[7],
+               p.x * g_m[2] + p.y * g_m[5] + p.z * g_m[8]);
+    }
+    const bool p = ok1(r, d.x, d.y, d.z), rej = gate(r, d.x, d.y, d.z);
     f.cases++; f.ok1_true += p; f.gate_rejects += rej; f.violations += p && rej;
     if (r.g[6] < INFINITY) f.e_finite++; else f.e_inf++;
 }
@@ -298,7 +376,19 @@ V3 dir_to(const Case& c, double u, double v)
 
 int adversarial_mode(int argc, char **argv)
 {
-    if (argc < 4) { std::fprintf(stderr, "usage: record_gate_check adversarial seed cases_per_family\n"); return 2; }
+    if (argc != 4 && argc != 13)
+    {
+        std::fprintf(stderr, "usage: record_gate_check adversarial seed cases_per_family [m0 .. m8]\n");
+        return 2;
+    }
+    if (argc == 13)
+    {
+        float m[9];
+        for (int k = 0; k < 9; k++) m[k] = std::strtof(argv[4 + k], nullptr);
+        set_matrix(m);
+    }
+    const float ident[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 };
+    const double bound = rtk::cam_dir_bound(g_have_m ? g_m : ident);
     Rng g(std::strtoull(argv[2], nullptr, 0));
     const uint64_t N = std::strtoull(argv[3], nullptr, 0);
     std::vector<Fam> fams;
@@ -476,7 +566,8 @@ int adversarial_mode(int argc, char **argv)
         }
         fams.push_back(f);
     }
-    std::printf("{\"mode\": \"adversarial\", \"families\": {");
+    std::printf("{\"mode\": \"adversarial\", \"cam_bound\": %.17g, \"gate_ok\": %s, \"families\": {", bound,
+                rtk::cam_gate_ok(bound) ? "true" : "false");
     for (size_t i = 0; i < fams.size(); i++)
         std::printf("%s\n  \"%s\": {\"cases\": %llu, \"ok1_true\": %llu, \"gate_rejects\": %llu, \"violations\": %llu, "
                     "\"e_finite\": %llu, \"e_inf\": %llu}", i ? "," : "", fams[i].name, (unsigned long long)fams[i].cases,
@@ -493,6 +584,17 @@ int main(int argc, char **argv)
 {
     if (argc >= 2 && std::string(argv[1]) == "scene") return scene_mode(argc, argv);
     if (argc >= 2 && std::string(argv[1]) == "adversarial") return adversarial_mode(argc, argv);
-    std::fprintf(stderr, "usage: record_gate_check scene|adversarial ...\n");
+    if (argc == 11 && std::string(argv[1]) == "bound")
+    {
+        float m[9];
+        for (int k = 0; k < 9; k++) m[k] = std::strtof(argv[2 + k], nullptr);
+        const double b = rtk::cam_dir_bound(m);
+        std::printf("{\"finite\": %s, \"cam_bound\": %.17g, \"gate_ok\": %s, \"fast_rcp_ok\": %s, \"gate_dmax\": %.17g, "
+                    "\"rcp_max_dir\": %.17g}\n", std::isfinite(b) ? "true" : "false", std::isfinite(b) ? b : -1.0,
+                    rtk::cam_gate_ok(b) ? "true" : "false", rtk::cam_fast_rcp_ok(b) ? "true" : "false", rtk::kGateDmax,
+                    rtk::kCamRcpMaxDir);
+        return 0;
+    }
+    std::fprintf(stderr, "usage: record_gate_check scene|adversarial|bound ...\n");
     return 2;
 }

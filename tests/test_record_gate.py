@@ -10,13 +10,25 @@ restated operation for operation):
     .. 2^39, components above 2^40 where the bound must be +inf);
   * selectivity: on scene 8 the wave-level pass rate of the gate over wave-uniform lists of 8 records or
     more exceeds the ok1 vote's by at most 0.01 absolute (an always-pass gate would be sound too).
+
+The bound E of a gate record holds for direction components up to kGateDmax = 1.0001.  rt_frame.cam's 3x3 need not
+be orthonormal and the direction is normalised BEFORE it, so the library bounds |D_i| per frame from the matrix
+(csrc/rt_cam_bound.h, rtk::cam_dir_bound -- the checker compiles the same function and reports it) and launches a
+frame above the bound without gate records.  With tests/camera_matrices.py's matrices:
+
+  * every matrix the library keeps the gate for is sound on all eight families (200,000 cases each);
+  * at S = 1024 the gate is NOT sound (u_lines, vertex_edge_hits): why the fall-back exists;
+  * on the frozen sliver scene (tests/golden/cameras.json) the wave vote skips a record a lane passes at S = 1024 --
+    the wrong pixel of tests/test_gpu_camera_matrices.py -- and none at S = 1.
 """
 import json
 import os
 import subprocess
+from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
+import camera_matrices as C
 from conftest import ROOT
 
 SCENES = (1, 4, 5, 8)
@@ -79,3 +91,103 @@ def test_gate_never_rejects_a_passing_lane_on_adversarial_family(adversarial, fa
         assert rep["e_finite"] == 0 and rep["gate_rejects"] == 0, rep
     else:
         assert rep["e_finite"] > 0 and rep["ok1_true"] > 0, rep       # the family does reach passing lanes
+
+
+# ------------------------------------------------------------------ cameras whose 3x3 is not orthonormal
+CAM_CASES = 200_000
+FX = C.fixture()
+MATRICES = [(base, n, C.from_bits(cams[n])) for base, cams in sorted(FX["cams"].items()) for n in C.FACTOR_NAMES if n in cams]
+CAM_OF = {(base, n): cam for base, n, cam in MATRICES}
+
+
+@pytest.fixture(scope="module")
+def bounds(checker):
+    """{(base, factor): the checker's `bound` report}: rtk::cam_dir_bound and what the library does with it."""
+    return {(base, n): run(checker, "bound", *C.hexf(C.m9_of(cam))) for base, n, cam in MATRICES}
+
+
+@pytest.fixture(scope="module")
+def gated_matrices(checker, bounds):
+    """The adversarial families through every matrix that keeps the gate, eight runs at a time."""
+    keep = [(base, n, cam) for base, n, cam in MATRICES if bounds[(base, n)]["gate_ok"]]
+    with ThreadPoolExecutor(max_workers=8) as pool:
+        reps = list(pool.map(lambda m: run(checker, "adversarial", 20261019, CAM_CASES, *C.hexf(C.m9_of(m[2]))), keep))
+    return {(base, n): r for (base, n, _), r in zip(keep, reps)}
+
+
+def test_cam_bound_sorts_the_matrices(bounds):
+    """Which factors keep the gate and the fast reciprocal, by the function the library calls: the column norm of
+    the 3x3 times (1 + 2^-20).  1 + 2^-14 is inside kGateDmax, 1 + 2^-13 and 1 + 2^-12 are not."""
+    gate = {"identity", "scale_2^-45", "scale_2^-20", "scale_2^-10", "scale_2^-1", "scale_1/3", "scale_1+2^-14", "mirror",
+            "rank2"}
+    fast = gate | {"scale_2^1", "scale_3", "scale_1+2^-13", "scale_1+2^-12", "diag_1_4_1/4", "shear"}
+    for (base, n), b in bounds.items():
+        assert b["finite"] and b["gate_dmax"] == 1.0001 and b["rcp_max_dir"] == 8.0, b
+        assert b["gate_ok"] == (n in gate), (base, n, b)
+        assert b["fast_rcp_ok"] == (n in fast), (base, n, b)
+        m = C.m9_of(CAM_OF[(base, n)]).astype("f8").reshape(3, 3)
+        norm = float((m * m).sum(0).max() ** 0.5)
+        assert norm <= b["cam_bound"] <= norm * (1 + 2.0 ** -19), (base, n, b, norm)
+
+
+def test_cam_bound_of_a_non_finite_matrix_fails_both(checker):
+    for bad in ("nan", "inf", "-inf"):
+        for at in range(9):
+            m = ["1", "0", "0", "0", "1", "0", "0", "0", "1"]
+            m[at] = bad
+            b = run(checker, "bound", *m)
+            assert not b["gate_ok"] and not b["fast_rcp_ok"] and not b["finite"], (bad, at, b)
+
+
+def test_gate_is_sound_for_every_matrix_that_keeps_it(gated_matrices):
+    assert len(gated_matrices) == 9 * 6              # nine factors keep the gate, on six base cameras
+    for key, rep in gated_matrices.items():
+        assert rep["gate_ok"], key
+        assert set(rep["families"]) == set(FAMILIES)
+        for fam, r in rep["families"].items():
+            assert r["cases"] >= CAM_CASES and r["violations"] == 0, (key, fam, r)
+    # ... and not vacuously: the checker aims each family through the inverse matrix, so it reaches passing lanes
+    # under a rotated, a mirrored and a shrinking camera alike
+    for key in (("sliver", "identity"), ("scene8", "mirror"), ("inside", "scale_1/3"), ("scene1", "scale_2^-1")):
+        for fam, r in gated_matrices[key]["families"].items():
+            if fam != "components_above_2^40":
+                assert r["ok1_true"] > 0 and r["e_finite"] > 0, (key, fam, r)
+
+
+def test_gate_is_not_sound_at_1024(checker, bounds):
+    """The gate's bound E is computed for unit directions: at S = 1024 it rejects lanes the first half passes.  This
+    is why the library drops the gate for such frames; a guard "simplified" away would leave these violations in
+    the kernel."""
+    for base in ("sliver", "look_at"):
+        assert not bounds[(base, C.S1024)]["gate_ok"]
+        cam = CAM_OF[(base, C.S1024)]
+        rep = run(checker, "adversarial", 20261019, CAM_CASES, *C.hexf(C.m9_of(cam)))
+        assert not rep["gate_ok"]
+        for fam in ("u_lines", "vertex_edge_hits"):
+            print(base, fam, rep["families"][fam])
+            assert rep["families"][fam]["violations"] > 0, (base, fam)
+
+
+def test_wave_vote_skips_a_passing_record_on_the_sliver_scene(checker, tmp_path):
+    """Scene mode on the frozen sliver scene (nine records, the sliver in the middle; 64x64x4, the suite's sample
+    offsets, one cell): at S = 1024 the gate vote of some wave rejects the sliver's record in every lane while a
+    lane's first half passes it -- the gated loop would skip it unloaded; with the orthonormal camera, none."""
+    tris, cam = C.cell_scenes(FX)["sliver9_4"]
+    hs = C.host_scene(tris, cam)
+    path = str(tmp_path / "sliver.rtscene")
+    try:
+        hs.save(path)
+    finally:
+        hs.close()
+    reps = {}
+    for n in ("identity", C.S1024, "scale_2^20"):
+        m = C.from_bits(FX["cams"]["sliver"][n])
+        reps[n] = run(checker, "scene", path, C.W, C.H, C.SPP, 1, 8, "--cam", *C.hexf(m), "--grid-res", 1,
+                      "--offsets", *C.hexf(C.OFFSETS))
+        print(n, reps[n])
+        assert reps[n]["one_origin"] and reps[n]["long_records"] == 9 * (C.W // 4) * (C.H // 4), reps[n]
+        assert reps[n]["ok1_true"] > 0
+    assert reps["identity"]["gate_ok"] and reps["identity"]["wholly_gated_ok1"] == 0 and reps["identity"]["violations"] == 0
+    assert not reps[C.S1024]["gate_ok"] and reps[C.S1024]["wholly_gated_ok1"] >= 1
+    assert reps["scale_2^20"]["wholly_gated_ok1"] >= 1
+    assert {n: {k: r[k] for k in FX["sliver"]["gate_check"][n]} for n, r in reps.items()} == FX["sliver"]["gate_check"]
