@@ -26,7 +26,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 KERNEL_SOURCES = ("csrc/rt_kernels.hip", "csrc/rt_walk.h", "csrc/rt_kparams.h", "csrc/rt_plan.hip",
                   "csrc/rt_scene.h", "csrc/rt_tracer.hip", "csrc/rt_grid_build.hip", "csrc/rt_device.h",
                   "csrc/rt_internal.h", "csrc/rt_box_words.h", "csrc/rt_fref_slots.h", "csrc/rt_cam_bound.h", "csrc/rt_record_gate.h", "csrc/rt_setup_div.h", "csrc/rt_rays.hip",
-                  "csrc/rt_ray_common.h", "csrc/rt_occlusion.hip", "csrc/rt_ao.hip", "csrc/Makefile",
+                  "csrc/rt_ray_common.h", "csrc/rt_occlusion.hip", "csrc/rt_ao.hip", "csrc/rt_distance.hip",
+                  "csrc/rt_dist_tree.h", "csrc/Makefile",
                   "../include/rt_tracer.h")
 
 
@@ -57,6 +58,7 @@ RT_ISECT_BRUTE_FORCE = 1
 RT_ISECT_RAY_MARCH = 2
 RT_RAYS_COUNT, RT_RAYS_SORT = 1, 2      # rt_trace_rays_device flags
 RT_AO_ROTATE = 1                        # rt_render_ao_device flags
+RT_DIST_EXHAUSTIVE, RT_DIST_SORT = 1, 2  # rt_distance_points_device flags
 AO_MAX_DIRS = 64
 SHARD_TILE = 16
 
@@ -71,7 +73,7 @@ TRACER_SYMBOLS = [
     "rt_host_free", "rt_render_hits_device", "rt_scene_info_get", "rt_build_hash", "rt_render_batch_device",
     "rt_render_records_device", "rt_render_frame_host_tiled", "rt_fref_buffer_bytes",
     "rt_trace_rays_device", "rt_primary_rays_device", "rt_occluded_rays_device",
-    "rt_ao_table", "rt_ao_rotations", "rt_render_ao_device",
+    "rt_ao_table", "rt_ao_rotations", "rt_render_ao_device", "rt_distance_points_device",
 ]
 MAX_BATCH = 10                           # frames per rt_render_batch_device launch (kMaxBatch)
 
@@ -135,6 +137,10 @@ class RayHit(ctypes.Structure):             # rt_ray_hit, 16 B
     _fields_ = [("tri", c_u32), ("t", c_f32), ("u", c_f32), ("v", c_f32)]
 
 
+class PointDistRec(ctypes.Structure):       # rt_point_dist, 8 B
+    _fields_ = [("dist", c_f32), ("tri", c_u32)]
+
+
 class AoParams(ctypes.Structure):           # rt_ao_params
     _fields_ = [("num_dirs", c_u32), ("tmin", c_f32), ("tmax", c_f32), ("dirs", ctypes.POINTER(c_f32)),
                 ("flags", c_u32)]
@@ -163,6 +169,11 @@ RAY_HIT_DTYPE = np.dtype([("tri", "<u4"), ("t", "<f4"), ("u", "<f4"), ("v", "<f4
 RAY_WORDS, RAY_HIT_WORDS, SAMPLE_REC_WORDS = 6, 4, 12     # 32-bit words of rt_ray, rt_ray_hit, rt_sample_rec
 # GpuScene.trace_rays' result: per-ray columns, the raw rt_ray_hit words and (count=True) the records
 RayHits = collections.namedtuple("RayHits", ["tri", "t", "u", "v", "hits", "rec"])
+# rt_point_dist (rt_distance_points_device): no triangle below FLT_MAX is dist FLT_MAX, tri 0xFFFFFFFF
+POINT_DIST_DTYPE = np.dtype([("dist", "<f4"), ("tri", "<u4")])
+POINT_WORDS, POINT_DIST_WORDS = 3, 2
+# GpuScene.distance's result: per-point columns, the closest points (or None) and the raw rt_point_dist words
+PointDist = collections.namedtuple("PointDist", ["dist", "tri", "closest", "raw"])
 
 _tracer = None
 _host = None
@@ -221,6 +232,8 @@ def tracer_lib():
             L.rt_ao_table.argtypes = [c_u32, vp]
             L.rt_ao_rotations.argtypes = [vp]
             L.rt_render_ao_device.argtypes = [vp, ctypes.POINTER(Frame), ctypes.POINTER(AoParams), vp, vp, vp]
+        if hasattr(L, "rt_distance_points_device"):  # absent in earlier builds (A/B runs)
+            L.rt_distance_points_device.argtypes = [vp, vp, c_u32, c_u32, vp, vp, vp]
         L.rt_unshard_device.argtypes = [c_u32, c_u32, c_u32, vp, vp, vp]
         L.rt_last_kernel_ms.argtypes = [vp, ctypes.POINTER(c_f32)]
         L.rt_trace_samples.argtypes = [vp, ctypes.POINTER(Frame), c_u32, c_u32, c_u32, c_u32, vp]
@@ -859,6 +872,62 @@ class GpuScene:
                 torch.cuda.synchronize(dev)            # the copy below runs on torch's stream
             return occ.cpu().numpy().astype(bool)
         return occ
+
+    def distance(self, points, closest=False, exhaustive=False, sort=False, stream=None):
+        """rt_distance_points_device: Renderer::DistanceBruteForce for caller-supplied points [n, 3] -- per point the
+        minimum of DistancePointTri over every triangle, bit for bit, and the lowest mesh triangle index that
+        attains it (include/rt_tracer.h has the contract).
+
+        points: a contiguous float32 torch CUDA tensor on the scene's device -- read in place through data_ptr(),
+        asynchronously on `stream` as trace_rays does, results as torch tensors on that device -- or a C-contiguous
+        float32 numpy array, which is uploaded and the results downloaded (synchronous).  Anything else (another
+        dtype, shape, device, a strided view, a CPU tensor) raises ValueError before any launch.
+
+        Returns PointDist: dist f32 [n] (FLT_MAX when no triangle lies below it), tri u32 [n] (0xFFFFFFFF then; int32
+        bits where torch has no uint32), closest f32 [n, 3] (closest=True: the point of triangle tri the distance
+        was measured to; else None), raw = the [n, 2] rt_point_dist words.  exhaustive=True (RT_DIST_EXHAUSTIVE)
+        evaluates every triangle for every point; sort=True (RT_DIST_SORT) takes the points in Morton order of
+        their position -- for points in no useful order.  Both give the same bytes, in input order."""
+        import torch
+        host = isinstance(points, np.ndarray)
+        if host:
+            if (points.dtype != np.float32 or points.ndim != 2 or points.shape[1] != POINT_WORDS or
+                    not points.flags["C_CONTIGUOUS"]):
+                raise ValueError("points: a C-contiguous float32 array of shape [n, 3]")
+            d_pts = torch.from_numpy(points).to(f"cuda:{self.device}")
+        elif isinstance(points, torch.Tensor):
+            if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != POINT_WORDS:
+                raise ValueError("points: a float32 tensor of shape [n, 3]")
+            if not points.is_cuda or points.device.index != self.device:
+                raise ValueError(f"points: a tensor on cuda:{self.device} (host memory is not read in place)")
+            if not points.is_contiguous():
+                raise ValueError("points: a contiguous tensor (a strided view would be read as other points)")
+            d_pts = points
+        else:
+            raise ValueError("points: a torch CUDA tensor or a numpy array")
+        n = d_pts.shape[0]
+        dev = d_pts.device
+        raw = torch.empty((n, POINT_DIST_WORDS), dtype=torch.int32, device=dev)
+        cl = torch.empty((n, 3), dtype=torch.float32, device=dev) if closest else None
+        flags = (RT_DIST_EXHAUSTIVE if exhaustive else 0) | (RT_DIST_SORT if sort else 0)
+        if stream is not None and int(stream) != torch.cuda.current_stream(dev).cuda_stream:
+            ext = torch.cuda.ExternalStream(int(stream), device=dev)                  # (as trace_rays)
+            for o in (raw, cl):
+                if o is not None:
+                    o.record_stream(ext)
+        L = tracer_lib()
+        _check(L.rt_distance_points_device(self._h, ctypes.c_void_p(d_pts.data_ptr()), n, flags,
+                                           ctypes.c_void_p(raw.data_ptr()),
+                                           ctypes.c_void_p(cl.data_ptr() if closest and n else 0),
+                                           ctypes.c_void_p(self._stream(torch, stream))), L, "rt_distance_points_device")
+        if host:
+            if stream is not None:
+                torch.cuda.synchronize(dev)            # the copies below run on torch's stream
+            r = raw.cpu().numpy().view(POINT_DIST_DTYPE).reshape(n)
+            return PointDist(r["dist"], r["tri"], cl.cpu().numpy() if closest else None, r)
+        u32 = getattr(torch, "uint32", None)
+        tri = raw[:, 1].view(u32) if u32 is not None else raw[:, 1]
+        return PointDist(raw[:, 0].view(torch.float32), tri, cl, raw)
 
     def render_ao(self, frame, num_dirs=4, tmin=0.0, tmax=float("inf"), dirs=None, rotate=True, out=None,
                   counts=False, stream=None):

@@ -349,5 +349,31 @@ struct KAo
 static_assert(sizeof(KAo) <= 4096, "kernel arguments");
 using ao_fn = void (*)(KAo);
 ao_fn render_ao_kernel(int var);
+// rt_distance.hip: k_distance_points<exhaustive>(KDist) and k_point_keys(KDist, keys) -- rt_distance_points_device.
+// The distance queries have a parameter struct of their own (KParams is the render kernels'): the arrays
+// rt_scene_create wrote for them (rt_dist_tree.h) and the call's pointers.
+constexpr uint32_t kDistLevels = 5;     // = kDistMaxLevels (rt_dist_tree.h)
+constexpr uint32_t kDistSmallBlocks = 2;    // a mesh of at most this many blocks: the default arm is the exhaustive kernel
+struct KDist
+{
+    const float4 *tri_dist;             // per sorted record: the distance record (rtd::dist_point_tri)
+    const uint32_t *tri_idx;            // per sorted record: its mesh triangle
+    const float4 *blk;                  // per block of kDistBlock records: {box min, -}{box max, -}
+    const uint32_t *blk_key;            // per block: Morton code of its first record
+    const float4 *nodes;                // the upper levels' boxes, same layout
+    uint32_t ntris, nblk, nlevels;
+    uint32_t lvl_off[kDistLevels], lvl_n[kDistLevels];
+    float scene_scale;                  // max |vertex coordinate|
+    float vmin[3], vinv[3];             // the vertex box's min and 1024 / extent (0 for a flat axis)
+    const float *points;                // [n][3]
+    const unsigned long long *order;    // RT_DIST_SORT: lane k takes point order[k] >> 32; else null
+    uint32_t n;
+    uint2 *out;                         // [n] rt_point_dist
+    float *closest;                     // [n][3] or null
+};
+using dist_fn = void (*)(KDist);
+using point_keys_fn = void (*)(KDist, unsigned long long *);
+dist_fn distance_points_kernel(bool exhaustive);
+point_keys_fn point_keys_kernel();
 
 } // namespace rtk

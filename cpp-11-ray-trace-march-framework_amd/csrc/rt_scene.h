@@ -93,6 +93,11 @@ struct rt_scene
     float4 *d_refs = nullptr, *d_shade = nullptr, *d_facen = nullptr;
     float4 *d_trimt = nullptr, *d_tridist = nullptr, *d_distblk = nullptr;
     uint32_t ndist_blk = 0;
+    // the distance queries' arrays (rt_dist_tree.h; rt_distance_points_device): sorted record -> mesh triangle,
+    // every block's first Morton code, and the box hierarchy over the blocks (upper levels back to back)
+    uint32_t *d_distidx = nullptr, *d_distkey = nullptr;
+    float4 *d_distnodes = nullptr;
+    uint32_t dist_levels = 0, dist_lvl_off[rtk::kDistLevels] = {}, dist_lvl_n[rtk::kDistLevels] = {};
     float scene_scale = 0.0f;
     float vmin[3] = { 0, 0, 0 }, vmax[3] = { 0, 0, 0 };
     uint64_t device_bytes = 0;

@@ -434,6 +434,47 @@ int  rt_ao_rotations(float *out_cs);
 int  rt_render_ao_device(rt_scene *scene, const rt_frame *frame, const rt_ao_params *ao,
                          uint32_t *d_bgra, uint8_t *d_counts, void *hip_stream);
 
+/* ---- distance queries ------------------------------------------------------------------
+ * Renderer::DistanceBruteForce (renderer.cpp:138-155) over DistancePointTri (triangle.h:174-198) for points the
+ * CALLER supplies -- baking a distance field, proximity tests, sphere-tracing the caller's own rays -- instead of
+ * the ray march's (RT_ISECT_RAY_MARCH). */
+typedef struct rt_point_dist { float dist; uint32_t tri; } rt_point_dist;   /* 8 B */
+enum rt_dist_flags {
+    RT_DIST_EXHAUSTIVE = 1,  /* every triangle for every point, no culling: the A/B and parity arm */
+    RT_DIST_SORT       = 2,  /* evaluate the points in Morton order of their position, so that a wave's points lie
+                                together: for points in no useful order.  Same bytes, in input order.  The sort, its
+                                scratch and its rules are RT_RAYS_SORT's */
+};
+/* Point p = d_points[i] gives, in d_out[i] (input order; exactly n records are written):
+ *   dist  what the reference's loop leaves, bit for bit (renderer.cpp:143-152, in mesh order):
+ *             dist = FLT_MAX;
+ *             for every triangle j: dist = std::min(dist, DistancePointTri(p, v0, v1, v2));
+ *         std::min(dist, d) is (d < dist) ? d : dist, so a NaN or an infinite d is never selected: dist is never NaN,
+ *         and it is FLT_MAX when no triangle's distance lies below that.
+ *   tri   the lowest mesh triangle index j whose d_j == dist, 0xFFFFFFFF if there is none.  The reference keeps no
+ *         index, so this is a definition; it makes the result independent of the order of evaluation.
+ * d_closest (optional, may be NULL): d_closest[i] = the point q of triangle tri that the reference measured to -- in
+ * the inside branch BarycentricInterpolate(u, v, v0, v1, v2) (triangle.h:189), else the proj of the segment whose
+ * LineSegMinDistSq the expression std::min(l01, std::min(l02, l12)) returns (triangle.h:194-196; on ties l01 wins
+ * over the inner minimum and l02 over l12).  With tri == 0xFFFFFFFF, q = (0, 0, 0).  Hence, with d = p - q,
+ * sqrtf((d.x*d.x + d.y*d.y) + d.z*d.z) == dist, bit for bit.
+ * No point is special-cased: the reference's loop is defined for NaN, +-inf, denormal and huge coordinates, and the
+ * result is that loop's.  The default arm skips triangles through a box hierarchy over Morton-ordered blocks of 32
+ * (a node is skipped for a point only when its float box distance minus 1e-5 (|p|_inf + max |vertex coordinate|)
+ * exceeds the point's running minimum; a NaN bound never skips); RT_DIST_EXHAUSTIVE evaluates every triangle, and so
+ * does the default arm on a mesh of at most 64 triangles, where there is nothing to skip.  Both give the same bytes.
+ * DESIGN.md §4.31
+ *   n == 0: RT_OK, nothing written.  n < 2^31.  A NULL scene, d_points or d_out, a d_points or d_closest that is not
+ *   4-byte aligned, a d_out that is not 8-byte aligned, or an unknown flag: RT_E_INVALID before any launch.
+ * Asynchronous on hip_stream.  Without RT_DIST_SORT the call is stateless: no lock, no event, no allocation, only
+ * arrays rt_scene_create wrote are read, it needs no ordering against the scene's render launches and can be captured
+ * in a graph.  With RT_DIST_SORT it shares the state of RT_RAYS_SORT and follows its rules (the scene's mutex, the
+ * sort scratch kept on the scene and grown -- with a device wait -- only when n exceeds every earlier sorted n,
+ * sorted calls of one scene ordered after each other); the sort word of point i is i << 32 | the Morton code of the
+ * point clamped into the vertex box. */
+int  rt_distance_points_device(rt_scene *scene, const float *d_points /* [n][3] */, uint32_t n, uint32_t flags,
+                               rt_point_dist *d_out, float *d_closest /* [n][3] or NULL */, void *hip_stream);
+
 /* Render-kernel time of the last timed rendering call on this scene (ms): the HIP events on the
  * launch stream immediately around its render kernel(s), as rt_kernel_times.  Waits for them. */
 int  rt_last_kernel_ms(rt_scene *scene, float *ms);

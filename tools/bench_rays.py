@@ -24,9 +24,14 @@ same session, into profiles/occlusion_bench.json (occlusion_legs).
 --ao measures rt_render_ao_device (GpuScene.render_ao), the AO frame in one launch, against the composition it fuses
 on the same frame, in the same session, into profiles/ao_bench.json (ao_legs).
 
+--distance measures rt_distance_points_device (GpuScene.distance) on jittered hit points and uniform points: the
+default arm against RT_DIST_EXHAUSTIVE and a chunked torch brute force, into profiles/distance_bench.json
+(distance_legs).
+
     python3 tools/bench_rays.py --parent-lib librt_tracer_parent.so [--ab-lib other=librt_tracer_other.so]
     python3 tools/bench_rays.py --occlusion
     python3 tools/bench_rays.py --ao
+    python3 tools/bench_rays.py --distance
 """
 import argparse
 import importlib.util
@@ -78,18 +83,21 @@ def warm(fn, warmup, clock_warmup=0.2):
     torch.cuda.synchronize()
 
 
-def measure(fns, n_items, steps, warmup):
-    """fns: {arm: callable}; samples interleaved over the arms.  Per arm: median ms, items/s, spread."""
-    for fn in fns.values():
-        warm(fn, warmup)
+def measure(fns, n_items, steps, warmup, per_arm=None):
+    """fns: {arm: callable}; samples interleaved over the arms.  Per arm: median ms, items/s, spread.
+    per_arm: {arm: (steps, warmup, n_items)} for arms that are timed over fewer launches or items."""
+    per_arm = per_arm or {}
+    for k, fn in fns.items():
+        w = per_arm.get(k, (steps, warmup, n_items))[1]
+        warm(fn, w, clock_warmup=0.2 if w == warmup else 0.0)
     ms = {k: [] for k in fns}
     for _ in range(5):
         for k, fn in fns.items():
-            ms[k].append(sample(fn, steps))
+            ms[k].append(sample(fn, per_arm.get(k, (steps, warmup, n_items))[0]))
     out = {}
     for k, v in ms.items():
         med = float(np.median(v))
-        out[k] = {"ms": round(med, 4), "per_s": round(n_items / (med * 1e-3), 1),
+        out[k] = {"ms": round(med, 4), "per_s": round(per_arm.get(k, (steps, warmup, n_items))[2] / (med * 1e-3), 1),
                   "spread": round((max(v) - min(v)) / med, 4), "samples_ms": [round(x, 4) for x in v]}
     return out
 
@@ -310,6 +318,110 @@ def ao_legs(args):
     print("wrote", args.out)
 
 
+def torch_brute_distance(points, v0, v1, v2, chunk=1024):
+    """What a caller has without GpuScene.distance: DistancePointTri's formulas (inside branch or the nearest of the
+    three edges) over points x triangles in float32 torch, `chunk` points at a time, reduced with min.  torch fuses
+    and orders the sums as it likes, so the result is NOT the reference's bits."""
+    e0, e1, e12 = v2 - v0, v1 - v0, v2 - v1
+    d00, d01, d11, d1212 = (e0 * e0).sum(1), (e0 * e1).sum(1), (e1 * e1).sum(1), (e12 * e12).sum(1)
+    inv = 1.0 / (d00 * d11 - d01 * d01)
+    out = torch.empty(points.shape[0], dtype=torch.float32, device=points.device)
+
+    def seg(p, a, ab, ll):
+        t = (((p[:, None, :] - a[None]) * ab[None]).sum(2) / ll[None]).clamp(0.0, 1.0)
+        q = a[None] + t[:, :, None] * ab[None]
+        return ((p[:, None, :] - q) ** 2).sum(2)
+
+    for i in range(0, points.shape[0], chunk):
+        p = points[i:i + chunk]
+        w = p[:, None, :] - v0[None]
+        d02, d12 = (w * e0[None]).sum(2), (w * e1[None]).sum(2)
+        u = (d00[None] * d12 - d01[None] * d02) * inv[None]
+        v = (d11[None] * d02 - d01[None] * d12) * inv[None]
+        q = v1[None] * u[:, :, None] + v2[None] * v[:, :, None] + v0[None] * (1.0 - u - v)[:, :, None]
+        inside = ((p[:, None, :] - q) ** 2).sum(2)
+        edges = torch.minimum(seg(p, v0, e1, d11), torch.minimum(seg(p, v0, e0, d00), seg(p, v1, e12, d1212)))
+        d2 = torch.where((u >= 0) & (v >= 0) & (u + v < 1), inside, edges)
+        out[i:i + chunk] = torch.nan_to_num(d2, nan=float("inf")).min(1).values.sqrt()
+    return out
+
+
+def distance_legs(args):
+    """--distance: rt_distance_points_device (GpuScene.distance) into profiles/distance_bench.json.  Points: the hit
+    points of the 1920x1080x1 primary rays jittered by a normal of 1 % of the box diagonal (seed 47) -- in camera
+    order, shuffled (PCG64(41)), shuffled with RT_DIST_SORT -- and as many uniform points in 1.5 x the box.  Arms,
+    samples interleaved (measure): the default (the box hierarchy), RT_DIST_EXHAUSTIVE, and a chunked float32 torch
+    brute force (torch_brute_distance: what a caller has today; not bit-exact; timed over the leg's first
+    TORCH_POINTS points).  `beats_exhaustive`: the default arm is faster by more than the larger spread."""
+    TORCH_POINTS = 1 << 15
+    rtm = load("rtm_this", None)
+    res = {"tool": "tools/bench_rays.py --distance", "frame": [W, H, 1], "steps": args.steps, "warmup": args.warmup,
+           "samples": 5, "build_hash": rtm.library_build_hash(), "device": torch.cuda.get_device_name(0),
+           "torch_arm": f"chunked float32 brute force over the first {TORCH_POINTS} points of a leg; not bit-exact",
+           "flat_sweep": "the flat sweep of all block boxes (compile-time RT_DIST_FLAT) lost to the hierarchy and was "
+                         "removed; profiles/distance_bench.json was written while it existed and holds its figures "
+                         "(flat_sweep_ab), and the culled kernel's on scene 1 (small_mesh_culled)",
+           "scenes": {}}
+    st = torch.cuda.current_stream().cuda_stream
+    for sid in args.scenes:
+        hs = rtm.HostScene.load(sid)
+        gs = rtm.GpuScene(hs, 0)
+        rays = gs.primary_rays(gs.frame(W, H, 1))
+        hits = gs.trace_rays(rays)
+        hit = hits.hits[:, 0] != -1
+        v, t = hs.mesh()
+        pos = torch.from_numpy(np.ascontiguousarray(v[:, :3])).cuda()
+        idx = torch.from_numpy(np.ascontiguousarray(t[:, :3]).astype(np.int64)).cuda()
+        v0, v1, v2 = pos[idx[:, 0]].contiguous(), pos[idx[:, 1]].contiguous(), pos[idx[:, 2]].contiguous()
+        lo, hi = pos.min(0).values, pos.max(0).values
+        diag = float((hi - lo).norm())
+        g = torch.Generator(device="cuda")
+        g.manual_seed(47)
+        p = rays[hit, :3] + rays[hit, 3:] * hits.t[hit][:, None]
+        p = (p + torch.randn(p.shape, generator=g, device="cuda") * (0.01 * diag)).contiguous()
+        n = p.shape[0]
+        perm = torch.from_numpy(np.random.Generator(np.random.PCG64(41)).permutation(n)).cuda()
+        mid = 0.5 * (lo + hi)
+        uni = (mid + (torch.rand((n, 3), generator=g, device="cuda") - 0.5) * 1.5 * (hi - lo)).contiguous()
+        torch.cuda.synchronize()
+        entry = {"triangles": int(t.shape[0]), "points": int(n), "box_diagonal": diag}
+
+        def leg(q, sort=False):
+            a = gs.distance(q, closest=True, sort=sort)
+            b = gs.distance(q, closest=True, sort=sort, exhaustive=True)
+            same = bool(torch.equal(a.raw, b.raw) and torch.equal(a.closest.view(torch.int32), b.closest.view(torch.int32)))
+            sub = q[:TORCH_POINTS].contiguous()
+            tb = torch_brute_distance(sub, v0, v1, v2)
+            err = float((tb - a.dist[:sub.shape[0]]).abs().max())
+            out = measure({"default": lambda: gs.distance(q, sort=sort, stream=st),
+                           "exhaustive": lambda: gs.distance(q, sort=sort, exhaustive=True, stream=st),
+                           "torch_brute_force": lambda: torch_brute_distance(sub, v0, v1, v2)}, n, args.steps, args.warmup,
+                          per_arm={"exhaustive": (2, 1, n), "torch_brute_force": (1, 1, sub.shape[0])})
+            for k in out:
+                out[k]["unit"] = "points/s"
+            d, e = out["default"], out["exhaustive"]
+            spread = max(d["spread"], e["spread"])
+            return {"points": int(n), "sort": sort, "exhaustive_same_bytes": same, "torch_max_abs_diff": err, **out,
+                    "speedup_over_exhaustive": round(e["ms"] / d["ms"], 3),
+                    "speedup_over_torch": round(d["per_s"] / out["torch_brute_force"]["per_s"], 3),
+                    "larger_spread": spread, "beats_exhaustive": bool(d["ms"] < e["ms"] * (1.0 - spread))}
+
+        entry["camera_order"] = leg(p)
+        shuffled = p[perm].contiguous()
+        entry["shuffled"] = leg(shuffled)
+        entry["shuffled_sorted"] = leg(shuffled, sort=True)
+        entry["uniform"] = leg(uni)
+        res["scenes"][str(sid)] = entry
+        print(json.dumps({str(sid): entry}), flush=True)
+        gs.close()
+        hs.close()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print("wrote", args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", type=int, nargs="+", default=[8, 1])
@@ -319,14 +431,17 @@ def main():
     ap.add_argument("--ab-lib", action="append", default=[], help="NAME=LIB: the ray legs from another build too")
     ap.add_argument("--occlusion", action="store_true", help="the occlusion legs (occlusion_legs) instead of the ray legs")
     ap.add_argument("--ao", action="store_true", help="the AO-frame legs (ao_legs) instead of the ray legs")
+    ap.add_argument("--distance", action="store_true", help="the distance-query legs (distance_legs) instead of the ray legs")
     ap.add_argument("--out", default=None, help="default: profiles/rays_bench.json (--occlusion: profiles/occlusion_bench.json; "
-                                                "--ao: profiles/ao_bench.json)")
+                                                "--ao: profiles/ao_bench.json; --distance: profiles/distance_bench.json)")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "ao_bench.json" if args.ao else
+        args.out = os.path.join(ROOT, "profiles", "ao_bench.json" if args.ao else "distance_bench.json" if args.distance else
                                 "occlusion_bench.json" if args.occlusion else "rays_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_rays.py measures on the GPU; none is visible")
+    if args.distance:
+        return distance_legs(args)
     if args.ao:
         return ao_legs(args)
     if args.occlusion:
