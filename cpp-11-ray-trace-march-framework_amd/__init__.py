@@ -25,7 +25,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # Everything librt_tracer.so is compiled from: PMC counter files are valid only for this hash
 KERNEL_SOURCES = ("csrc/rt_kernels.hip", "csrc/rt_walk.h", "csrc/rt_kparams.h", "csrc/rt_plan.hip",
                   "csrc/rt_scene.h", "csrc/rt_tracer.hip", "csrc/rt_grid_build.hip", "csrc/rt_device.h",
-                  "csrc/rt_internal.h", "csrc/rt_box_words.h", "csrc/rt_fref_slots.h", "csrc/rt_cam_bound.h", "csrc/rt_record_gate.h", "csrc/rt_setup_div.h", "csrc/rt_rays.hip",
+                  "csrc/rt_internal.h", "csrc/rt_box_words.h", "csrc/rt_fref_slots.h", "csrc/rt_cam_bound.h", "csrc/rt_record_gate.h", "csrc/rt_setup_div.h", "csrc/rt_miss_mask.h", "csrc/rt_rays.hip",
                   "csrc/rt_ray_common.h", "csrc/rt_occlusion.hip", "csrc/rt_ao.hip", "csrc/rt_distance.hip",
                   "csrc/rt_dist_tree.h", "csrc/Makefile",
                   "../include/rt_tracer.h")
@@ -74,6 +74,7 @@ TRACER_SYMBOLS = [
     "rt_render_records_device", "rt_render_frame_host_tiled", "rt_fref_buffer_bytes",
     "rt_trace_rays_device", "rt_primary_rays_device", "rt_occluded_rays_device",
     "rt_ao_table", "rt_ao_rotations", "rt_render_ao_device", "rt_distance_points_device",
+    "rt_debug_miss_mask",
 ]
 MAX_BATCH = 10                           # frames per rt_render_batch_device launch (kMaxBatch)
 
@@ -249,6 +250,8 @@ def tracer_lib():
             L.rt_debug_wide_items.argtypes = [vp, ctypes.POINTER(c_u32)]
         L.rt_debug_wide_tiers.argtypes = [vp, ctypes.POINTER(c_u32), ctypes.POINTER(c_u32)]
         L.rt_debug_set_plan_delay.argtypes = [vp, c_u32]
+        if hasattr(L, "rt_debug_miss_mask"):         # absent in earlier builds (A/B runs)
+            L.rt_debug_miss_mask.argtypes = [vp, ctypes.POINTER(c_u32), ctypes.POINTER(c_u32)]
         if hasattr(L, "rt_scene_set_timing"):
             L.rt_scene_set_timing.argtypes = [vp, c_u32]
         L.rt_sample_table.argtypes = [c_u32, vp]
@@ -726,6 +729,14 @@ class GpuScene:
         L = tracer_lib()
         a, b = c_u32(), c_u32()
         _check(L.rt_debug_wide_tiers(self._h, ctypes.byref(a), ctypes.byref(b)), L, "rt_debug_wide_tiers")
+        return a.value, b.value
+
+    def miss_mask(self):
+        """(work items the most recent frame's miss mask flags -- 0 without a mask --, masks computed so far)
+        (rt_debug_miss_mask)."""
+        L = tracer_lib()
+        a, b = c_u32(), c_u32()
+        _check(L.rt_debug_miss_mask(self._h, ctypes.byref(a), ctypes.byref(b)), L, "rt_debug_miss_mask")
         return a.value, b.value
 
     def last_kernel_ms(self):

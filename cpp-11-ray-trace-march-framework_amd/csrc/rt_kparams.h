@@ -176,7 +176,22 @@ struct KParams
                                 // (read after the walk through late_params; NULL in the plain calls)
     rt_sample_rec *recs;        // debug kernel only
     uint32_t rec_x0, rec_y0, rec_w, rec_h;
+    // the miss skip (null: every item is traced): one bit per work item of the launch in its
+    // natural order (local tile k * items per tile + item in tile), set by k_miss_mask where every sample of
+    // the item provably misses the grid box (rt_miss_mask.h); and the packed word of an all-miss pixel per row
+    const uint32_t *miss_mask;
+    const uint32_t *rowmiss;    // [H], written by the same k_miss_mask launch
 };
+
+// A miss-mask buffer (rt_scene::miss[]): two counter words (flagged items, finished workgroups: k_miss_mask's
+// ticket), the row table, then the mask bits as 64-bit words (one ballot each).
+constexpr uint32_t kMissHead = 2;
+__host__ __device__ inline size_t miss_mask_offset(uint32_t H) { return (size_t(kMissHead) + H + 1u) & ~size_t(1); }   // in u32 words, even
+inline size_t miss_buffer_words(uint32_t H, uint32_t n_items) { return miss_mask_offset(H) + 2u * ((size_t(n_items) + 63u) / 64u); }
+// k_miss_mask(P, n_items, buf, host_cnt, tag): buf as above; host_cnt: a host-mapped word, tag | flagged items (24
+// bits, saturating) once the last workgroup has finished; tag = (0x80 | the mask's generation) << 24
+using miss_mask_fn = void (*)(KParams, uint32_t, uint32_t *, uint32_t *, uint32_t);
+miss_mask_fn miss_mask_kernel();
 
 // A frame shape's camera-space tables (KParams::ndcx / ndcy, smp), written on the device by
 // k_frame_tables from rtd::cam_x / cam_y (the host's restatement uses the same IEEE operations).

@@ -7,6 +7,7 @@
 #include <utility>
 #include <cstring>
 
+#include "rt_miss_mask.h"
 #include "rt_scene.h"
 #include "rt_walk.h"
 
@@ -207,7 +208,66 @@ __global__ void __launch_bounds__(kWG) k_hf_plan(KParams P, uint32_t nblocks, ui
     }
 }
 
+// The miss mask of one launch, on the frame's stream before its render kernel: thread i takes work
+// item i of the launch's NATURAL order (local tile i >> ipt_shift, independent of tile_order), finds the range
+// of the camera-space table entries its valid lanes read and asks rt_miss_mask.h whether every ray of that
+// rectangle misses the grid box; the wave's ballot is one 64-bit word of the mask.  An item is 64 / spp pixels
+// of a tile in Morton order, a 2^a x 2^b block: its lanes 0 and 63 (process_item's own coordinates,
+// slot_coord_m) are its corners, clipped to the region as `valid` clips them.  Threads below H also write the
+// row table.  The last workgroup hands the flagged count to the host and re-arms the counters (as k_hf_plan).
+__global__ void __launch_bounds__(kWG) k_miss_mask(KParams P, uint32_t n_items, uint32_t *buf, uint32_t *host_cnt,
+                                                   uint32_t tag)
+{
+    __shared__ uint32_t s_last;
+    const uint32_t i = blockIdx.x * kWG + threadIdx.x;
+    if (i < P.H) buf[kMissHead + i] = row_miss_word(P, i);
+    bool flag = false;
+    if (i < n_items)
+    {
+        const uint32_t k = i >> P.ipt_shift, slot0 = (i - (k << P.ipt_shift)) << 6;
+        const ItemCoord a = slot_coord_m(P, k, slot0), b = slot_coord_m(P, k, slot0 + 63u);
+        if (a.valid)
+        {
+            const uint32_t x1 = min(b.x, P.rx0 + P.rw - 1u), y1 = min(b.y, P.ry0 + P.rh - 1u);
+            float xlo = P.ndcx[a.x * P.spp], xhi = xlo, ylo = P.ndcy[a.y * P.spp], yhi = ylo;
+            bool nan = false;           // (a NaN entry fails every compare, so it is looked for by itself)
+            for (uint32_t j = a.x * P.spp; j < (x1 + 1u) * P.spp; j++)
+            {
+                const float v = P.ndcx[j];
+                xlo = v < xlo ? v : xlo;
+                xhi = v > xhi ? v : xhi;
+                nan = nan || v != v;
+            }
+            for (uint32_t j = a.y * P.spp; j < (y1 + 1u) * P.spp; j++)
+            {
+                const float v = P.ndcy[j];
+                ylo = v < ylo ? v : ylo;
+                yhi = v > yhi ? v : yhi;
+                nan = nan || v != v;
+            }
+            flag = !nan && provably_misses(P.m, P.org, P.bmin, P.bmax, xlo, xhi, ylo, yhi);
+        }
+    }
+    const unsigned long long bal = __ballot(flag);
+    if ((threadIdx.x & 63u) == 0u && (i & ~63u) < n_items)
+    {
+        reinterpret_cast<unsigned long long *>(buf + miss_mask_offset(P.H))[i >> 6] = bal;
+        if (bal) atomicAdd(&buf[0], uint32_t(__popcll(bal)));
+    }
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0u) s_last = atomicAdd(&buf[1], 1u) == gridDim.x - 1u;
+    __syncthreads();
+    if (!s_last || threadIdx.x != 0u) return;
+    __threadfence();
+    *host_cnt = tag | min(atomicAdd(&buf[0], 0u), 0x00FFFFFFu);     // tag: 0x80 | the mask's generation, in the top byte
+    buf[0] = 0u;
+    buf[1] = 0u;
+}
+
 } // namespace
+
+miss_mask_fn miss_mask_kernel() { return k_miss_mask; }
 
 // k_hf_plan after a measured frame.  A plan lists a block only against the PREVIOUS measurement (its
 // maximum and span decide the thresholds), so the first measured frame of a launch shape listed

@@ -76,6 +76,44 @@ struct HfCtx
 
 } // namespace rtk
 
+namespace rtk {
+
+// What a miss mask (k_miss_mask) was computed for: the camera, the frame shape and the version of
+// its camera-space tables (rt_scene::tab_epoch: the sample table, the field of view and the shape again), the
+// region and the shard.  Compared bytewise (zeroed before it is filled).
+struct MissKey
+{
+    float m[9], org[3];
+    uint32_t W, H, spp, rx0, ry0, rw, rh, rank, nranks, tiles_x, n_items, pad;
+    uint64_t tab_epoch;
+};
+
+// One of a scene's two mask buffers (layout: miss_buffer_words).  A buffer is rewritten only by a k_miss_mask
+// launch that is ordered after every launch that read it: rt_scene::miss_busy lists the buffers a launch not
+// yet ordered before the next one may read, and a buffer whose only reader so far ran on the writer's own
+// stream is ordered by that stream (rd_*).
+struct MissSlot
+{
+    uint32_t *d = nullptr;
+    size_t cap = 0;                     // u32 words
+    bool valid = false;
+    MissKey key;
+    uint64_t stamp = 0;                 // rt_scene::miss_clock at its last use (computed or handed to a frame)
+    uint32_t tag = 0x80000000u;         // (0x80 | generation) << 24: what its k_miss_mask puts above the count
+    hipStream_t rd_stream = nullptr;    // the stream of its last reader since it was computed ...
+    bool rd_any = false, rd_multi = false;  // ... whether there was one, and whether readers ran on two streams
+    // its k_miss_mask: the stream it ran on and an event recorded after it; a reader on another stream -- an
+    // overlapped launch orders only after the launch two back -- waits for it until it has been seen complete
+    hipStream_t wr_stream = nullptr;
+    hipEvent_t wr_ev = nullptr;
+    bool wr_done = false;
+};
+
+constexpr uint32_t kMissSeen = 4;       // unmasked keys remembered: a key gets a mask at its second request
+constexpr uint64_t kMissKeep = 8;       // a mask used within this many requests keeps its buffer (> 2 + kMissSeen)
+
+} // namespace rtk
+
 constexpr uint32_t kTimeRing = 64;  // rt_kernel_times: launches kept
 constexpr uint32_t kTimeEvery = 8;  // default: every 8th launch gets the timed event pair
 constexpr uint32_t kMaxBands = 64;   // rt_render_frame_host: row bands per frame
@@ -116,7 +154,22 @@ struct rt_scene
     float4 *d_gates[2] = { nullptr, nullptr };
     bool rec_gate = true;
     rtk::FrefSlots fref;
-    uint64_t *d_clk = nullptr;      // RT_KERNEL_FLAG_WAVE_CLOCK records of the last such launch
+    // The miss skip: two mask buffers under the record buffers' discipline -- a frame whose key is
+    // in neither computes its mask into one that no launch still in flight reads, or is traced without a mask
+    // (always exact).  h_miss_cnt[b]: host-mapped, the mask's tag | flagged items once buffer b's k_miss_mask has
+    // finished; a mask known to flag nothing is not handed to the kernel.
+    rtk::MissSlot miss[2];
+    uint32_t *h_miss_cnt = nullptr, *d_miss_cnt = nullptr;
+    uint32_t miss_busy = 0;         // buffers read by launches the next launch is not yet ordered after
+    uint32_t miss_last = 0;         // buffers the scene's last launch reads
+    bool miss_skip = true;          // RT_MISS_SKIP=0 at rt_scene_create: no masks (the A/B arm)
+    uint64_t tab_epoch = 0;         // bumped whenever the camera-space tables are rewritten (ndc_key changes)
+    uint64_t miss_clock = 0;        // mask requests so far (ensure_miss_mask)
+    rtk::MissKey miss_seen[rtk::kMissSeen];     // the last keys that were traced without a mask (a ring)
+    uint32_t miss_seen_n = 0, miss_seen_next = 0;
+    uint32_t miss_computed = 0;     // rt_debug_miss_mask: masks computed so far ...
+    int miss_frame_slot = -1;       // ... and the buffer the most recent frame reads (-1: none)
+    uint64_t *d_clk = nullptr;     // RT_KERNEL_FLAG_WAVE_CLOCK records of the last such launch
     size_t clk_cap = 0;
     uint32_t clk_items = 0;
     // AUTO heavy-first order: per launch shape, which blocks the previous frame found heavy

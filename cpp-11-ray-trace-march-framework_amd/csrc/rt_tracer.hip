@@ -201,6 +201,7 @@ int wait_scene_idle(rt_scene *s)
     if (s->ev_prev) RT_HIP(hipEventSynchronize(s->ev_prev->ev));
     s->ev_prev.reset();
     rtk::fref_ordered(s->fref);                 // nothing still reads a per-origin record buffer
+    s->miss_busy = 0u;                          // ... or a miss mask
     return RT_OK;
 }
 
@@ -222,6 +223,7 @@ hipError_t wait_unless_done(hipStream_t st, hipEvent_t e)
 int order_all(rt_scene *s, hipStream_t st)
 {
     rtk::fref_ordered(s->fref);
+    s->miss_busy = 0u;                          // (the miss masks likewise)
     if (!s->ev_recorded) return RT_OK;
     if (st != s->last_stream) RT_HIP(wait_unless_done(st, s->ev_last->ev));
     if (s->ev_prev && s->prev_stream != st) RT_HIP(wait_unless_done(st, s->ev_prev->ev));
@@ -234,6 +236,7 @@ int order_all(rt_scene *s, hipStream_t st)
 // after the one before that (at most two in flight)
 int order_overlap(rt_scene *s, hipStream_t st)
 {
+    s->miss_busy = s->miss_last;                // the last launch's miss masks may still be read
     if (s->ev_prev && s->prev_stream != st) RT_HIP(wait_unless_done(st, s->ev_prev->ev));
     s->ev_prev = s->ev_last;
     s->prev_stream = s->last_stream;
@@ -296,6 +299,7 @@ int prepare_ndc(rt_scene *s, const rt_frame *f, uint32_t spp, const std::vector<
     for (uint32_t y = 0; y < f->height; y++)
         for (uint32_t k = 0; k < spp; k++) hy[size_t(y) * spp + k] = rtd::cam_y(y, tbl[2 * k + 1], f->height, fx, aspect);
     if (int rc = wait_scene_idle(s)) return rc;
+    s->tab_epoch++;
     if (n > s->ndc_cap)
     {
         if (s->d_ndc) RT_HIP(hipFree(s->d_ndc));
@@ -354,6 +358,7 @@ int prepare_samples(rt_scene *s, const rt_frame *f, uint32_t spp)
             s->tab.spp = spp;
             std::memcpy(s->tab.smp, tbl.data(), tbl.size() * sizeof(float));
             s->tab_dirty = true;
+            s->tab_epoch++;
             s->ndc_key = key;
             s->ndc_w = f->width;
             s->ndc_spp = spp;
@@ -523,6 +528,135 @@ int ensure_origin_terms(rt_scene *s, KParams& P, hipStream_t st, uint32_t busy, 
     return RT_OK;
 }
 
+// The miss mask of one frame of a lane-kernel launch (P complete: region, shard, ipt_shift, tiles_x_m),
+// n_items work items, on stream st after the frame's tables (flush_tables) and before its render kernel.  The
+// callers pass AUTO's lane kernels on the grid walk only -- no wave clocks, no hit IDs, no records, no stream
+// capture (a captured k_miss_mask has not run when the next frame asks for its count).  Sets P.miss_mask /
+// P.rowmiss, or leaves them null -- the kernel then traces every item, which is always exact --: the skip is
+// off, the origin is inside the box, the frame's mask is known to flag nothing, or both buffers are read by
+// launches this one is not ordered after.  *used: the scene's buffers the launch reads so far (this frame's
+// is added; a buffer in it is not rewritten for a later frame of the same launch).
+// A mask pays only where its key repeats, so a key gets one when it is asked for the SECOND time while still among
+// the last kMissSeen unmasked keys: a camera that moves every frame never launches k_miss_mask.  And a buffer
+// whose mask was used within the last kMissKeep requests is not evicted: keys that rotate through the two buffers
+// (three row bands per frame) settle on two masked keys and the others unmasked instead of recomputing one per
+// request (more than 2 + kMissSeen rotating keys are never seen twice; fewer reuse a buffer within kMissKeep).
+int ensure_miss_mask(rt_scene *s, KParams& P, uint32_t n_items, hipStream_t st, uint32_t *used)
+{
+    P.miss_mask = P.rowmiss = nullptr;
+    s->miss_frame_slot = -1;
+    if (!s->miss_skip || !s->h_miss_cnt || n_items == 0u) return RT_OK;
+    bool inside = true;
+    for (int a = 0; a < 3; a++) inside = inside && P.org[a] >= P.bmin[a] && P.org[a] <= P.bmax[a];
+    if (inside) return RT_OK;                                   // rtd::point_in_aabb: nothing misses the box
+    rtk::MissKey key;
+    std::memset(&key, 0, sizeof(key));
+    std::memcpy(key.m, P.m, sizeof(key.m));
+    std::memcpy(key.org, P.org, sizeof(key.org));
+    key.W = P.W; key.H = P.H; key.spp = P.spp;
+    key.rx0 = P.rx0; key.ry0 = P.ry0; key.rw = P.rw; key.rh = P.rh;
+    key.rank = P.rank; key.nranks = P.nranks; key.tiles_x = P.tiles_x; key.n_items = n_items;
+    key.tab_epoch = s->tab_epoch;
+    const uint64_t now = ++s->miss_clock;
+    auto hand = [&](int b) {
+        s->miss[b].stamp = now;
+        P.rowmiss = s->miss[b].d + kMissHead;
+        P.miss_mask = s->miss[b].d + miss_mask_offset(P.H);
+        s->miss_frame_slot = b;
+        *used |= 1u << b;
+    };
+    for (int b = 0; b < 2; b++)
+        if (s->miss[b].valid && std::memcmp(&s->miss[b].key, &key, sizeof(key)) == 0)
+        {
+            // finished and nothing flagged: the frame stops paying for the mask (the word carries the tag of the
+            // k_miss_mask that wrote it: an earlier mask of this buffer that finishes late is not mistaken for it)
+            rtk::MissSlot& m = s->miss[b];
+            if (*static_cast<volatile uint32_t *>(s->h_miss_cnt + b) == m.tag)
+            {
+                m.stamp = now;
+                return RT_OK;
+            }
+            if (!m.wr_done && st != m.wr_stream)
+            {
+                if (hipEventQuery(m.wr_ev) == hipSuccess) m.wr_done = true;
+                else RT_HIP(hipStreamWaitEvent(st, m.wr_ev, 0));
+            }
+            hand(b);
+            return RT_OK;
+        }
+    int b = -1;
+    for (int c = 0; c < 2; c++)
+    {
+        const rtk::MissSlot& m = s->miss[c];
+        const bool writable = !((s->miss_busy >> c) & 1u) || (m.rd_any && !m.rd_multi && m.rd_stream == st);
+        if (((*used >> c) & 1u) || !writable) continue;
+        if (m.valid && now - m.stamp <= rtk::kMissKeep) continue;         // in use: not evicted
+        if (b < 0 || !m.valid || (s->miss[b].valid && m.stamp < s->miss[b].stamp)) b = c;
+    }
+    int seen = -1;
+    for (uint32_t i = 0; i < s->miss_seen_n; i++)
+        if (std::memcmp(&s->miss_seen[i], &key, sizeof(key)) == 0) seen = int(i);
+    if (seen < 0)
+    {
+        // the key's first request: remembered, traced without a mask
+        s->miss_seen[s->miss_seen_next] = key;
+        s->miss_seen_next = (s->miss_seen_next + 1u) % rtk::kMissSeen;
+        s->miss_seen_n = std::min(s->miss_seen_n + 1u, rtk::kMissSeen);
+        return RT_OK;
+    }
+    if (b < 0) return RT_OK;
+    s->miss_seen[seen].n_items = 0u;                            // (no frame has n_items == 0: the entry matches nothing now)
+    rtk::MissSlot& m = s->miss[b];
+    const size_t need = miss_buffer_words(P.H, n_items);
+    if (need > m.cap)
+    {
+        // (every reader of the old buffer is ordered before st's next work, see above: st drained, it is free)
+        m.valid = false;
+        if (m.d)
+        {
+            RT_HIP(hipStreamSynchronize(st));
+            RT_HIP(hipFree(m.d));
+        }
+        m.d = nullptr;
+        m.cap = 0;
+        RT_HIP(hipMalloc(&m.d, need * sizeof(uint32_t)));
+        m.cap = need;
+        RT_HIP(hipMemsetAsync(m.d, 0, kMissHead * sizeof(uint32_t), st));     // the kernel re-arms them itself
+    }
+    m.tag = 0x80000000u | ((((m.tag >> 24) + 1u) & 0x7Fu) << 24);      // 0x80 | generation, count 0
+    *static_cast<volatile uint32_t *>(s->h_miss_cnt + b) = 0u;
+    const uint32_t threads = std::max((n_items + 63u) & ~63u, P.H);
+    // (the dispatch carries its completion event itself: no marker packet between it and the frame)
+    if (!m.wr_ev) RT_HIP(hipEventCreateWithFlags(&m.wr_ev, s->ev_order_flags));
+    hipExtLaunchKernelGGL(miss_mask_kernel(), dim3((threads + kWG - 1u) / kWG), dim3(kWG), 0, st, nullptr, m.wr_ev, 0u, P,
+                          n_items, m.d, s->d_miss_cnt + b, m.tag);
+    RT_HIP(hipGetLastError());
+    m.wr_stream = st;
+    m.wr_done = false;
+    m.key = key;
+    m.valid = true;
+    m.rd_any = m.rd_multi = false;
+    s->miss_computed++;
+    hand(b);
+    return RT_OK;
+}
+
+// The scene's launch on st reads the mask buffers `used` (0: none).  more: the launch runs beside the scene's
+// last one without the two being ordered here (rt_render_frame_host_tiled's row bands), so it adds to that one's.
+void miss_launched(rt_scene *s, uint32_t used, hipStream_t st, bool more)
+{
+    for (int b = 0; b < 2; b++)
+        if ((used >> b) & 1u)
+        {
+            rtk::MissSlot& m = s->miss[b];
+            m.rd_multi = m.rd_multi || (m.rd_any && m.rd_stream != st);
+            m.rd_stream = st;
+            m.rd_any = true;
+        }
+    s->miss_busy |= used;
+    s->miss_last = more ? (s->miss_last | used) : used;
+}
+
 // AUTO's own choice of the wide section for a single-frame launch: a shard of >= 2 ranks of a scene
 // with dense cells
 bool auto_wide(const rt_scene *s, const KParams& P)
@@ -603,6 +737,14 @@ int launch_render(rt_scene *s, const rt_frame *f, KParams& P, uint32_t n_local_t
         else if (lanes && P.isect == RT_ISECT_BRUTE_FORCE)
             var = kVarBrute;
     }
+    // the miss skip: AUTO's lane kernels on the grid walk (RT_KERNEL_LANES stays the unskipped arm), frames
+    // that ask for neither hit IDs nor records, outside a stream capture
+    uint32_t mused = 0;
+    s->miss_frame_slot = -1;
+    if (auto_path && kind == RT_KERNEL_AUTO && !(var & kVarWaveClock) && !P.hits && !P.recs &&
+        cap == hipStreamCaptureStatusNone)
+        if (int rc = ensure_miss_mask(s, P, uint32_t(blocks) * kWavesPerWG, st, &mused)) return rc;
+    miss_launched(s, mused, st, !order_streams);
     // kernel-time events only outside stream capture (a captured record has no time to read)
     // A timed event pair costs ~10 us of device time per launch (measured: bench step 0.755 ->
     // 0.736 ms without), so only every time_every-th launch is timed (rt_scene_set_timing)
@@ -887,6 +1029,7 @@ int launch_batch(rt_scene *const *S, const rt_frame *F, uint32_t n, KParams *P, 
     }
     // per-origin records of every frame, and the cross-stream order of every scene's state
     uint32_t used[kMaxBatch] = {};             // per frame: its scene's record buffers this launch reads
+    uint32_t mused[kMaxBatch] = {};            // ... and its scene's miss-mask buffers
     for (uint32_t i = 0; i < n; i++)
     {
         rt_scene *s = S[i];
@@ -911,12 +1054,17 @@ int launch_batch(rt_scene *const *S, const rt_frame *F, uint32_t n, KParams *P, 
             if (int rc = ensure_origin_terms(s, P[i], st, u, &u)) return rc;
             used[first] = u;
         }
+        // the frame's miss mask (as launch_render; mused: per scene, at its first frame's index)
+        if (!clk && cap == hipStreamCaptureStatusNone && !P[i].hits && !P[i].recs)
+            if (int rc = ensure_miss_mask(s, P[i], uint32_t(fblocks) * kWavesPerWG, st, &mused[first < 0 ? i : uint32_t(first)]))
+                return rc;
     }
     for (uint32_t i = 0; i < n; i++)
     {
         bool first = true;
         for (uint32_t j = 0; j < i; j++) first = first && S[j] != S[i];
         if (first) rtk::fref_launched(S[i]->fref, used[i]);
+        if (first) miss_launched(S[i], mused[i], st, false);
     }
     if (front || wide_heavy)
         if (int rc = hf_prepare(s0, P[0], blocks, kvar, front, st, ident | 1u, cams)) return rc;
@@ -1194,6 +1342,7 @@ int rt_scene_create(const rt_scene_desc *d, int device, rt_scene **out)
     s->wh_beta16 = env_tunable("RT_WH_BETA16", s->wh_beta16);
     s->hf_follow = env_tunable("RT_HF_FOLLOW", s->hf_follow);
     s->rec_gate = env_tunable("RT_REC_GATE", 1u) != 0u;         // 0: no record gate (the A/B arm)
+    s->miss_skip = env_tunable("RT_MISS_SKIP", 1u) != 0u;       // 0: no miss masks (the A/B arm)
     for (int a = 0; a < 3; a++)
     {
         s->dims[a] = g.dims[a];
@@ -1447,6 +1596,14 @@ int rt_scene_create(const rt_scene_desc *d, int device, rt_scene **out)
         RT_HIP(hipHostGetDevicePointer(&dev, s->h_wh_cnt, 0));
         s->d_wh_cnt = static_cast<uint32_t *>(dev);
     }
+    // the miss masks' flagged counts, one host-mapped word per buffer (k_miss_mask's last workgroup writes it)
+    RT_HIP(hipHostMalloc(&s->h_miss_cnt, sizeof(uint32_t) * 2, hipHostMallocMapped | hipHostMallocCoherent));
+    std::memset(s->h_miss_cnt, 0, sizeof(uint32_t) * 2);
+    {
+        void *dev = nullptr;
+        RT_HIP(hipHostGetDevicePointer(&dev, s->h_miss_cnt, 0));
+        s->d_miss_cnt = static_cast<uint32_t *>(dev);
+    }
     s->ndc_cap = size_t(4096 + 4096) * 16u;
     RT_HIP(hipMalloc(&s->d_ndc, s->ndc_cap * sizeof(float)));
     s->smp_cap = 64u;
@@ -1496,6 +1653,12 @@ int rt_scene_destroy(rt_scene *s)
             if (h.fence_ev) (void)hipEventDestroy(h.fence_ev);
         }
         if (s->h_wh_cnt) (void)hipHostFree(s->h_wh_cnt);
+        for (rtk::MissSlot& m : s->miss)
+        {
+            (void)hipFree(m.d);
+            if (m.wr_ev) (void)hipEventDestroy(m.wr_ev);
+        }
+        if (s->h_miss_cnt) (void)hipHostFree(s->h_miss_cnt);
         if (s->rays_ev_recorded) (void)hipEventSynchronize(s->rays_ev);
         rt_internal_sort_free(s->rays_sort);
         if (s->rays_ev) (void)hipEventDestroy(s->rays_ev);
@@ -1966,6 +2129,7 @@ int rt_render_frame_host_tiled(rt_scene *s, const rt_frame *f, uint32_t *h_tiles
         s->ev_prev.reset();
     }
     rtk::fref_ordered(s->fref);                 // (so either per-origin record buffer may be recomputed)
+    s->miss_busy = s->miss_last = 0u;           // (and either miss mask; the row-band launches below add theirs)
     KParams P0;
     frame_params(s, f, P0);
     if (use_lanes(f, spp) && P0.isect == RT_ISECT_GRID && P0.tri_test == RT_TRI_MOLLER_TRUMBORE &&
@@ -2433,6 +2597,19 @@ int rt_debug_wide_tiers(rt_scene *s, uint32_t *listed, uint32_t *lds)
     RT_HIP(hipMemcpy(&pl, c->plans + (nv & 1u), sizeof(pl), hipMemcpyDeviceToHost));
     *listed = std::min(pl.cnt_w, kWhMax);
     *lds = std::min(pl.cnt_l, kWhMax);
+    return RT_OK;
+}
+
+int rt_debug_miss_mask(rt_scene *s, uint32_t *flagged, uint32_t *computed)
+{
+    if (!s || !flagged || !computed) return fail(RT_E_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    int rc;
+    if ((rc = ensure_device(s))) return rc;
+    RT_HIP(hipDeviceSynchronize());
+    const int b = s->miss_frame_slot;
+    *flagged = b >= 0 ? (*static_cast<volatile uint32_t *>(s->h_miss_cnt + b) & 0x00FFFFFFu) : 0u;
+    *computed = s->miss_computed;
     return RT_OK;
 }
 

@@ -1313,6 +1313,9 @@ __device__ __forceinline__ bool ray_march(const KParams& P, float ox, float oy, 
 // and the walk's end cell (raw: a box-run miss's cell still in its box-word copy).
 struct SampleOut { bool hit; float t, u, v; uint32_t voxel, csr; };
 
+// renderer.cpp:121: the colour of a sample that hits nothing (trace_sample; row_miss_word)
+__device__ __forceinline__ float miss_colour(uint32_t py, uint32_t H) { return float(py) / float(H); }
+
 // renderer.cpp:88-122: one sample -> its colour contribution; hit_tri = the hit triangle
 // (Grid::Intersect's tri_idx, renderer.cpp:105) or kNoTri
 template <bool STATS, int TRI, int VAR>
@@ -1360,8 +1363,7 @@ __device__ __forceinline__ void trace_sample(const KParams& P, uint32_t px, uint
     }
     else
     {
-        const float m = float(py) / float(Q.H);                  // renderer.cpp:121
-        cr = cg = cb = m;
+        cr = cg = cb = miss_colour(py, Q.H);                     // renderer.cpp:121
     }
     hit_tri = hit ? tri : rtd::kNoTri;
     if (STATS)
@@ -1461,12 +1463,12 @@ __device__ __forceinline__ ItemCoord item_coord(const KParams& P, uint32_t item,
 // tile that overhangs the region (x or y up to 15 past it, past 2^16 too) is invalid exactly as
 // item_coord finds it: the Morton offsets come from the lane, the sample is the lane's low bits,
 // validity the same two compares.
-__device__ __forceinline__ ItemCoord item_coord_pre(const KParams& P, uint32_t item, uint32_t lane)
+// (slot_coord_m: sample slot `slot` of local tile k, tile_slot_coord with the shard deal's magic division; k_miss_mask
+// takes the corner lanes of an item in the launch's natural order from it)
+__device__ __forceinline__ ItemCoord slot_coord_m(const KParams& P, uint32_t k, uint32_t slot)
 {
-    const uint32_t kseq = item >> P.ipt_shift;                // position in the launch's tile order
-    const uint32_t slot = ((item - (kseq << P.ipt_shift)) << 6) + lane;
     ItemCoord ic;
-    ic.c.k = P.tile_order ? P.tile_order[kseq] : kseq;        // local tile k
+    ic.c.k = k;
     uint32_t tx, ty;
     shard_tile_xy_m(ic.c.k, P.rank, P.nranks, P.tiles_x, P.tiles_x_m, tx, ty);
     ic.c.tx0 = P.rx0 + tx * kTile;
@@ -1477,6 +1479,47 @@ __device__ __forceinline__ ItemCoord item_coord_pre(const KParams& P, uint32_t i
     ic.y = ic.c.ty0 + compact_bits(ic.p >> 1);
     ic.valid = ic.x < P.rx0 + P.rw && ic.y < P.ry0 + P.rh;
     return ic;
+}
+
+__device__ __forceinline__ ItemCoord item_coord_pre(const KParams& P, uint32_t item, uint32_t lane)
+{
+    const uint32_t kseq = item >> P.ipt_shift;                // position in the launch's tile order
+    const uint32_t slot = ((item - (kseq << P.ipt_shift)) << 6) + lane;
+    return slot_coord_m(P, P.tile_order ? P.tile_order[kseq] : kseq, slot);    // local tile k
+}
+
+// The miss skip: bit `local tile k * items per tile + item in tile` of KParams::miss_mask -- the
+// launch's NATURAL item order, whatever tile_order says -- is set when k_miss_mask proved that every sample of
+// the item misses the grid box (rt_miss_mask.h).  Wave-uniform: one scalar load and a bit test.
+__device__ __forceinline__ bool item_flagged(const KParams& P, uint32_t item, uint32_t k)
+{
+    const uint32_t idx = (k << P.ipt_shift) + (item & ((1u << P.ipt_shift) - 1u));
+    return ((P.miss_mask[idx >> 5] >> (idx & 31u)) & 1u) != 0u;
+}
+
+// The resolve of one pixel (renderer.cpp:124-133), shared by process_item and k_miss_mask's row table.
+// resolve_channel4: one channel of the spp-4 quad form, from the sum of its four samples (c * 0.25f is exact);
+// resolve_word: the generic form, from the three sums.
+__device__ __forceinline__ uint32_t resolve_channel4(float c) { return rtd::pack_channel(rtd::gamma_half(c * 0.25f)); }
+__device__ __forceinline__ uint32_t resolve_word(const KParams& Q, float sr, float sg, float sb)
+{
+    return rtd::pack_bgra8(rtd::gamma_half(average(Q, sr)), rtd::gamma_half(average(Q, sg)), rtd::gamma_half(average(Q, sb)));
+}
+
+// The packed BGRA word of a pixel of row y whose samples all miss (KParams::rowmiss[y]): process_item's own
+// sums and resolve on spp copies of the miss colour -- the quad form at spp 4 (the sum starts at the first
+// sample), the generic form otherwise (the sum starts at 0.0f).
+__device__ __forceinline__ uint32_t row_miss_word(const KParams& P, uint32_t y)
+{
+    const float c = miss_colour(y, P.H);
+    if (P.spp == 4u)
+    {
+        const uint32_t v = resolve_channel4(c + c + c + c);
+        return v | (v << 8) | (v << 16);
+    }
+    float sum = 0.0f;
+    for (uint32_t k = 0; k < P.spp; k++) sum += c;
+    return resolve_word(P, sum, sum, sum);
 }
 
 // The tile origin of an ItemCoord as one word held in a VGPR (the empty asm keeps the compiler from
@@ -1531,6 +1574,15 @@ __device__ __forceinline__ void process_item(const KParams& P, uint32_t item, ui
     uint32_t origin;
     {
         const ItemCoord ic = item_coord_pre(P, item, lane);
+        // the miss skip (AUTO's lane kernels on the grid walk; the host passes a mask only to frames without hit
+        // IDs or records): a flagged item's pixels take the row's all-miss word, and no ray is generated
+        if constexpr (TRI == RT_TRI_MOLLER_TRUMBORE && (VAR & kVarAutoCore) == kVarAutoCore &&
+                      (VAR & (kVarWaveClock | kVarLdsSplit | kVarMarch | kVarBrute | kVarRays)) == 0)
+            if (P.miss_mask && item_flagged(P, item, ic.c.k))
+            {
+                if (ic.valid && ic.s == 0) store_pixel(P, ic.c, ic.p, ic.x, ic.y, P.rowmiss[ic.y]);
+                return;
+            }
         origin = tile_origin_word(ic);
         if (ic.valid)
             trace_sample<false, TRI, VAR>(P, ic.x, ic.y, ic.s, cr, cg, cb, hit_tri, nullptr, off, &so);
@@ -1561,7 +1613,7 @@ __device__ __forceinline__ void process_item(const KParams& P, uint32_t item, ui
         // bytes meet in the pixel's lane by quad broadcasts (same per-channel arithmetic)
         const uint32_t j = lane & 3u;
         const float c = j == 0u ? sb : (j == 1u ? sg : sr);
-        uint32_t v = rtd::pack_channel(rtd::gamma_half(c * 0.25f)) << (8u * j);   // renderer.cpp:124, exact
+        uint32_t v = resolve_channel4(c) << (8u * j);            // renderer.cpp:124, exact
         v = j == 3u ? 0u : v;
         const uint32_t word = quad_bcast_u<0>(v) | quad_bcast_u<1>(v) | quad_bcast_u<2>(v);
         if (ic.valid && ic.s == 0 && owner) store_pixel(Q, ic.c, ic.p, ic.x, ic.y, word);
@@ -1579,9 +1631,7 @@ __device__ __forceinline__ void process_item(const KParams& P, uint32_t item, ui
     }
     if (ic.valid && ic.s == 0 && owner)
     {
-        const uint32_t word = rtd::pack_bgra8(rtd::gamma_half(average(Q, sr)), rtd::gamma_half(average(Q, sg)),
-                                              rtd::gamma_half(average(Q, sb)));
-        store_pixel(Q, ic.c, ic.p, ic.x, ic.y, word);
+        store_pixel(Q, ic.c, ic.p, ic.x, ic.y, resolve_word(Q, sr, sg, sb));
     }
 }
 

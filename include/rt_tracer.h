@@ -534,6 +534,12 @@ int rt_debug_set_plan_delay(rt_scene *s, uint32_t us);
 /* The same plan's items: *listed = all of them, *lds = those the LDS tier renders (the launch shape's
    section runs it: all of them, else 0; kVarLdsSplit, RT_WH_LDS).  Synchronises the device. */
 int rt_debug_wide_tiers(rt_scene *s, uint32_t *listed, uint32_t *lds);
+/* The miss skip (AUTO's lane kernels; RT_MISS_SKIP=0 at rt_scene_create turns it off): *flagged = work items
+   the miss mask of this scene's most recent frame flags -- items whose samples all provably miss the grid box
+   and that the kernel therefore did not trace --, 0 when that frame was launched without a mask; *computed =
+   masks computed for this scene so far (a mask is kept per camera, frame shape, sample table, region and
+   shard, two of them per scene).  Synchronises the device. */
+int rt_debug_miss_mask(rt_scene *s, uint32_t *flagged, uint32_t *computed);
 
 /* What rt_scene_create chose for a scene, and the scheduling tunables it read once from the
    environment (RT_HF_FLOOR, RT_HF_MIN_BLOCKS, RT_WH_FLOOR, RT_WH_ALPHA16, RT_WH_ALPHA16_N2,
