@@ -538,9 +538,10 @@ int ensure_origin_terms(rt_scene *s, KParams& P, hipStream_t st, uint32_t busy, 
 // is added; a buffer in it is not rewritten for a later frame of the same launch).
 // A mask pays only where its key repeats, so a key gets one when it is asked for the SECOND time while still among
 // the last kMissSeen unmasked keys: a camera that moves every frame never launches k_miss_mask.  And a buffer
-// whose mask was used within the last kMissKeep requests is not evicted: keys that rotate through the two buffers
-// (three row bands per frame) settle on two masked keys and the others unmasked instead of recomputing one per
-// request (more than 2 + kMissSeen rotating keys are never seen twice; fewer reuse a buffer within kMissKeep).
+// whose mask, of the current tables, was used within the last kMissKeep requests is not evicted: keys that rotate
+// through the two buffers (three row bands per frame) settle on two masked keys and the others unmasked instead of
+// recomputing one per request (more than 2 + kMissSeen rotating keys are never seen twice; fewer reuse a buffer
+// within kMissKeep).
 int ensure_miss_mask(rt_scene *s, KParams& P, uint32_t n_items, hipStream_t st, uint32_t *used)
 {
     P.miss_mask = P.rowmiss = nullptr;
@@ -590,7 +591,10 @@ int ensure_miss_mask(rt_scene *s, KParams& P, uint32_t n_items, hipStream_t st, 
         const rtk::MissSlot& m = s->miss[c];
         const bool writable = !((s->miss_busy >> c) & 1u) || (m.rd_any && !m.rd_multi && m.rd_stream == st);
         if (((*used >> c) & 1u) || !writable) continue;
-        if (m.valid && now - m.stamp <= rtk::kMissKeep) continue;         // in use: not evicted
+        // in use: not evicted -- unless it is of an earlier version of the tables (a change of fov, shape or sample
+        // table): tab_epoch only grows, so that key is never asked for again, and keeping its buffer would leave
+        // the frames after the change without a mask for up to kMissKeep requests
+        if (m.valid && m.key.tab_epoch == s->tab_epoch && now - m.stamp <= rtk::kMissKeep) continue;
         if (b < 0 || !m.valid || (s->miss[b].valid && m.stamp < s->miss[b].stamp)) b = c;
     }
     int seen = -1;

@@ -64,6 +64,7 @@ struct Scene
     V3 aabb_min, aabb_max;
     std::vector<uint32_t> off, refs;      // CSR of m_cells, GridIdx order
     double build_s = 0.0;
+    std::vector<float> smp;               // [2 spp] sample offsets for RenderTile (orc_render_smp); empty: Hammersley
 
     uint32_t GridIdx(uint32_t x, uint32_t y, uint32_t z) const   // grid.h:41-42
         { return x + z * dim[0] + y * dim[0] * dim[2]; }
@@ -572,7 +573,7 @@ inline V3 TraceSample(const Scene& s, const float* smp, uint32_t px, uint32_t py
 void RenderTile(const Scene& s, uint32_t W, uint32_t H, uint32_t spp, int tri_test,
                 uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint32_t *buf, uint32_t *hit_ids)
 {
-    const std::vector<float> smp = Hammersley(spp);
+    const std::vector<float> smp = s.smp.empty() ? Hammersley(spp) : s.smp;
     const uint32_t tw = x1 - x0;
     orc_rec rec;
     for (uint32_t y=y0; y<y1; y++)
@@ -644,6 +645,15 @@ orc_scene *orc_scene_load(const char *path)
     std::unique_ptr<orc_scene> h(new orc_scene());
     if (!ReadScene(path, h->s)) return nullptr;
     BuildGrid(h->s, 64);
+    return h.release();
+}
+
+// orc_scene_load with the grid's resolution given (Grid::Grid's parameter; scene.cpp:7 passes 64)
+orc_scene *orc_scene_load_res(const char *path, uint32_t grid_res)
+{
+    std::unique_ptr<orc_scene> h(new orc_scene());
+    if (grid_res == 0 || !ReadScene(path, h->s)) return nullptr;
+    BuildGrid(h->s, grid_res);
     return h.release();
 }
 
@@ -868,6 +878,21 @@ int orc_render_cam(const orc_scene *h, uint32_t W, uint32_t H, uint32_t spp, con
     orc_scene c = *h;
     std::memcpy(&c.s.cam[0][0], cam16, 64);
     c.s.fov = fov;
+    double sec = 0.0;
+    return orc_render(&c, W, H, spp, 0, 0, out, hit_ids, &sec);
+}
+
+// orc_render_cam with the caller's sample offsets (rt_frame.sample_offsets: smp[2 spp], (x, y) per sample) in place
+// of the Hammersley table; smp == NULL is orc_render_cam itself
+int orc_render_smp(const orc_scene *h, uint32_t W, uint32_t H, uint32_t spp, const float *cam16, float fov,
+                   const float *smp, uint32_t *out, uint32_t *hit_ids)
+{
+    if (!h || !cam16) return 1;
+    orc_scene c = *h;
+    std::memcpy(&c.s.cam[0][0], cam16, 64);
+    c.s.fov = fov;
+    spp = std::max(1u, spp);
+    if (smp) c.s.smp.assign(smp, smp + 2 * size_t(spp));
     double sec = 0.0;
     return orc_render(&c, W, H, spp, 0, 0, out, hit_ids, &sec);
 }

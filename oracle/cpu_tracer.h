@@ -44,6 +44,7 @@ typedef struct orc_rec {
 } orc_rec;
 
 orc_scene *orc_scene_load(const char *path);          /* NULL on error */
+orc_scene *orc_scene_load_res(const char *path, uint32_t grid_res);   /* ... with Grid::Grid's resolution (64 above) */
 void       orc_scene_free(orc_scene *s);
 int        orc_scene_info(const orc_scene *s, orc_info *out);
 /* offsets: num_cells+1 u32, refs: num_refs u32 (GridIdx order, ascending tri per cell) */
@@ -62,6 +63,10 @@ int orc_render(const orc_scene *s, uint32_t W, uint32_t H, uint32_t spp, uint32_
  * Scene::GetCameraParameters returns it, fov in degrees. */
 int orc_render_cam(const orc_scene *s, uint32_t W, uint32_t H, uint32_t spp, const float *cam16, float fov,
                    uint32_t *out_bgra, uint32_t *hit_ids);
+/* orc_render_cam with the caller's sample offsets smp[2 spp] (rt_frame.sample_offsets) in place of the
+   Hammersley table; smp NULL: the Hammersley table. */
+int orc_render_smp(const orc_scene *s, uint32_t W, uint32_t H, uint32_t spp, const float *cam16, float fov,
+                   const float *smp, uint32_t *out_bgra, uint32_t *hit_ids);
 /* Per-sample records for the pixel rectangle [x0,x0+w) x [y0,y0+h), order (y, x, s). */
 int orc_trace_samples(const orc_scene *s, uint32_t W, uint32_t H, uint32_t spp, uint32_t tri_test,
                       uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, orc_rec *out);

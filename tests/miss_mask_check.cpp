@@ -2,14 +2,25 @@
 // librt_tracer.so runs (provably_misses) against the oracle's GenRay / PointAABB / RayAABB on the kernel's own
 // work items -- 64 consecutive sample slots of a 16x16 tile in Morton order.
 //   g++ -O2 -std=c++17 -ffp-contract=off tests/miss_mask_check.cpp -o miss_mask_check
-//   miss_mask_check scene file.rtscene W H spp [rx0 ry0 rw rh [cam x16]]   a scene's box under its own or a given camera
-//   miss_mask_check families seed                                          seeded boxes and cameras
+//   miss_mask_check scene file.rtscene W H spp [rx0 ry0 rw rh [cam x16]] [key=value ...]
+//                                                    a scene's box under its own or a given camera
+//   miss_mask_check batch file.rtscene cases.txt     one case per line of cases.txt (the arguments of `scene` after
+//                                                    the file), the scene read once: {"masks": [...]} in line order
+//   miss_mask_check families seed                    seeded boxes and cameras
+// key=value (after the positional arguments, any order):
+//   fov=F            the field of view in degrees (strtof: a hex float is read exactly) instead of the scene's
+//   samples=FILE     2 spp raw float32: the sample offsets (rt_frame.sample_offsets) instead of the Hammersley table
+//   rank=R nranks=N  the work items of rank R of N (the whole frame only): the row-rotated deal of rt_kparams.h's
+//                    shard_tile_xy, restated here
+// (The box is the mesh's bounds +- 0.0001, whatever the grid's resolution: the checker builds the grid with ONE
+// cell, which a saved scene of any grid_res shares its box with.)
 // An item is FLAGGED when provably_misses holds for the range of its valid lanes' camera-space x and y (the
 // table entries rtd::cam_x / cam_y, as k_miss_mask takes them).  Required: no flagged item holds a sample that
 // passes PointAABB or RayAABB.  Reported: items, items whose samples all miss, flagged items.
 #include "../oracle/cpu_tracer.cpp"
 #include "../cpp-11-ray-trace-march-framework_amd/csrc/rt_miss_mask.h"
 
+#include <cctype>
 #include <cstdio>
 #include <cstring>
 #include <random>
@@ -35,8 +46,24 @@ struct Frame
     V3 bmin, bmax;
     uint32_t W, H, spp;
     uint32_t rx0, ry0, rw, rh;
+    uint32_t rank = 0, nranks = 1;  // the launch's tiles: every tile of the region, or a rank's share of the frame's
     std::vector<float> smp;         // [2 spp]
 };
+
+// the launch's tiles (tx, ty) in local-tile order: the region's, row-major -- or, of nranks > 1, those whose
+// row-rotated number ty * tiles_x + (tx + 3 ty) mod tiles_x is rank, rank + nranks, ... (rt_kparams.h kShardRot = 3)
+std::vector<std::pair<uint32_t, uint32_t>> launch_tiles(const Frame& f)
+{
+    const uint32_t tiles_x = (f.rw + 15) / 16, tiles_y = (f.rh + 15) / 16;
+    std::vector<std::pair<uint32_t, uint32_t>> out;
+    for (uint32_t t = f.rank; t < tiles_x * tiles_y; t += f.nranks)
+    {
+        const uint32_t ty = t / tiles_x, xr = t % tiles_x;
+        const uint32_t rot = f.nranks > 1 ? (3 * ty) % tiles_x : 0;
+        out.push_back({ (xr + tiles_x - rot) % tiles_x, ty });
+    }
+    return out;
+}
 
 // the camera-space x / y of GenRay (camera.h:20-21, 40-42), the operations of rtd::cam_x / cam_y
 float cam_x(const Frame& f, uint32_t px, float sx)
@@ -63,13 +90,13 @@ Acc check_frame(const Frame& f)
     for (int r = 0; r < 3; r++)
         for (int c = 0; c < 3; c++) m9[3 * r + c] = f.cam[r][c];
     const float bmn[3] = { f.bmin.x, f.bmin.y, f.bmin.z }, bmx[3] = { f.bmax.x, f.bmax.y, f.bmax.z };
-    const uint32_t tiles_x = (f.rw + 15) / 16, tiles_y = (f.rh + 15) / 16, ipt = 4 * f.spp;
+    const uint32_t ipt = 4 * f.spp;
     uint32_t shift = 0;
     while ((1u << shift) < f.spp) shift++;
-    for (uint32_t t = 0; t < tiles_x * tiles_y; t++)
+    for (const auto& tile : launch_tiles(f))
         for (uint32_t it = 0; it < ipt; it++)
         {
-            const uint32_t tx0 = f.rx0 + (t % tiles_x) * 16, ty0 = f.ry0 + (t / tiles_x) * 16;
+            const uint32_t tx0 = f.rx0 + tile.first * 16, ty0 = f.ry0 + tile.second * 16;
             bool any_valid = false, any_hit = false;
             float xlo = 0, xhi = 0, ylo = 0, yhi = 0;
             for (uint32_t lane = 0; lane < 64; lane++)
@@ -107,24 +134,117 @@ void print_acc(const char *name, const Acc& a, const char *tail)
                 (unsigned long long)a.flagged_with_hit, tail);
 }
 
-int scene_mode(int argc, char **argv)
+bool load_scene(const char *path, Scene& s)
 {
-    if (argc < 6) { std::fprintf(stderr, "usage: miss_mask_check scene file W H spp [rx0 ry0 rw rh [cam x16]]\n"); return 2; }
-    Scene s;
-    if (!ReadScene(argv[2], s)) { std::fprintf(stderr, "cannot read %s\n", argv[2]); return 1; }
-    BuildGrid(s, 64);
-    Frame f;
+    if (!ReadScene(path, s)) { std::fprintf(stderr, "cannot read %s\n", path); return false; }
+    BuildGrid(s, 1);                // (only the box is used, and it does not depend on the resolution)
+    return true;
+}
+
+// One case: W H spp [rx0 ry0 rw rh [cam x16]] [key=value ...]; false (and a message) when it cannot be read
+bool parse_case(const Scene& s, const std::vector<std::string>& a, Frame& f)
+{
+    std::vector<std::string> pos, kv;
+    for (const auto& t : a) (t.find('=') == std::string::npos ? pos : kv).push_back(t);
+    if (pos.size() != 3 && pos.size() != 7 && pos.size() != 23)
+    {
+        std::fprintf(stderr, "a case is W H spp [rx0 ry0 rw rh [cam x16]] [key=value ...]\n");
+        return false;
+    }
     std::memcpy(f.cam, s.cam, sizeof(f.cam));
     f.fov = s.fov;
     f.bmin = s.aabb_min; f.bmax = s.aabb_max;
-    f.W = std::atoi(argv[3]); f.H = std::atoi(argv[4]); f.spp = std::atoi(argv[5]);
+    f.W = std::atoi(pos[0].c_str()); f.H = std::atoi(pos[1].c_str()); f.spp = std::atoi(pos[2].c_str());
     f.rx0 = f.ry0 = 0; f.rw = f.W; f.rh = f.H;
-    if (argc >= 10) { f.rx0 = std::atoi(argv[6]); f.ry0 = std::atoi(argv[7]); f.rw = std::atoi(argv[8]); f.rh = std::atoi(argv[9]); }
-    if (argc >= 26)
-        for (int i = 0; i < 16; i++) f.cam[i / 4][i % 4] = std::strtof(argv[10 + i], nullptr);
+    if (pos.size() >= 7)
+    {
+        f.rx0 = std::atoi(pos[3].c_str()); f.ry0 = std::atoi(pos[4].c_str());
+        f.rw = std::atoi(pos[5].c_str()); f.rh = std::atoi(pos[6].c_str());
+    }
+    if (pos.size() == 23)
+        for (int i = 0; i < 16; i++) f.cam[i / 4][i % 4] = std::strtof(pos[7 + i].c_str(), nullptr);
+    if (f.W == 0 || f.H == 0 || f.spp == 0 || f.spp > 64 || (f.spp & (f.spp - 1)) || f.rw == 0 || f.rh == 0 ||
+        f.rx0 + f.rw > f.W || f.ry0 + f.rh > f.H)
+    {
+        std::fprintf(stderr, "bad frame shape, region or spp (a power of two <= 64)\n");
+        return false;
+    }
     f.smp = Hammersley(f.spp);
+    f.rank = 0; f.nranks = 1;
+    for (const auto& t : kv)
+    {
+        const std::string key = t.substr(0, t.find('=')), val = t.substr(t.find('=') + 1);
+        if (key == "fov") f.fov = std::strtof(val.c_str(), nullptr);
+        else if (key == "rank") f.rank = std::atoi(val.c_str());
+        else if (key == "nranks") f.nranks = std::atoi(val.c_str());
+        else if (key == "samples")
+        {
+            std::FILE *fp = std::fopen(val.c_str(), "rb");
+            const bool ok = fp && std::fread(f.smp.data(), sizeof(float), 2 * f.spp, fp) == 2 * f.spp && std::fgetc(fp) == EOF;
+            if (fp) std::fclose(fp);
+            if (!ok) { std::fprintf(stderr, "%s: not 2 x %u float32\n", val.c_str(), f.spp); return false; }
+        }
+        else { std::fprintf(stderr, "unknown key %s\n", key.c_str()); return false; }
+    }
+    if (f.nranks == 0 || f.rank >= f.nranks || (f.nranks > 1 && (f.rx0 || f.ry0 || f.rw != f.W || f.rh != f.H)))
+    {
+        std::fprintf(stderr, "bad rank / nranks (a shard is dealt from the whole frame)\n");
+        return false;
+    }
+    return true;
+}
+
+int scene_mode(int argc, char **argv)
+{
+    if (argc < 6) { std::fprintf(stderr, "usage: miss_mask_check scene file W H spp [rx0 ry0 rw rh [cam x16]] [key=value ...]\n"); return 2; }
+    Scene s;
+    if (!load_scene(argv[2], s)) return 1;
+    Frame f;
+    if (!parse_case(s, std::vector<std::string>(argv + 3, argv + argc), f)) return 2;
     std::printf("{\"mode\": \"scene\", ");
     print_acc("mask", check_frame(f), "}\n");
+    return 0;
+}
+
+int batch_mode(int argc, char **argv)
+{
+    if (argc != 4) { std::fprintf(stderr, "usage: miss_mask_check batch file cases.txt\n"); return 2; }
+    Scene s;
+    if (!load_scene(argv[2], s)) return 1;
+    std::FILE *fp = std::fopen(argv[3], "r");
+    if (!fp) { std::fprintf(stderr, "cannot read %s\n", argv[3]); return 1; }
+    std::string text;
+    for (int c; (c = std::fgetc(fp)) != EOF;) text.push_back(char(c));
+    std::fclose(fp);
+    std::vector<Acc> res;
+    for (size_t at = 0; at < text.size();)
+    {
+        size_t end = text.find('\n', at);
+        if (end == std::string::npos) end = text.size();
+        std::vector<std::string> tok;
+        for (size_t i = at; i < end;)
+        {
+            while (i < end && std::isspace(static_cast<unsigned char>(text[i]))) i++;
+            size_t j = i;
+            while (j < end && !std::isspace(static_cast<unsigned char>(text[j]))) j++;
+            if (j > i) tok.push_back(text.substr(i, j - i));
+            i = j;
+        }
+        at = end + 1;
+        if (tok.empty()) continue;
+        Frame f;
+        if (!parse_case(s, tok, f)) return 2;
+        res.push_back(check_frame(f));
+    }
+    std::printf("{\"mode\": \"batch\", \"masks\": [");
+    for (size_t i = 0; i < res.size(); i++)
+    {
+        const Acc& a = res[i];
+        std::printf("%s{\"items\": %llu, \"all_miss\": %llu, \"flagged\": %llu, \"flagged_with_hit\": %llu}", i ? ", " : "",
+                    (unsigned long long)a.items, (unsigned long long)a.all_miss, (unsigned long long)a.flagged,
+                    (unsigned long long)a.flagged_with_hit);
+    }
+    std::printf("]}\n");
     return 0;
 }
 
@@ -277,7 +397,8 @@ int families_mode(int argc, char **argv)
 int main(int argc, char **argv)
 {
     if (argc >= 2 && std::string(argv[1]) == "scene") return scene_mode(argc, argv);
+    if (argc >= 2 && std::string(argv[1]) == "batch") return batch_mode(argc, argv);
     if (argc >= 2 && std::string(argv[1]) == "families") return families_mode(argc, argv);
-    std::fprintf(stderr, "usage: miss_mask_check scene|families ...\n");
+    std::fprintf(stderr, "usage: miss_mask_check scene|batch|families ...\n");
     return 2;
 }

@@ -11,9 +11,7 @@ request (a camera that moves every frame never pays for one), so a frame is rend
 (tests/miss_mask_check.cpp) flags -- a mask that silently stayed null would pass every comparison of pixels.
 """
 import hashlib
-import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -21,6 +19,7 @@ import pytest
 import camera_matrices as cm
 import synth_scenes as ss
 from conftest import ROOT, load_package
+from miss_skip_cases import SETTLE, build_checker, cam16, cpu_mask, frame, gpu_scene, settled
 
 pytestmark = pytest.mark.gpu
 rtm = load_package()
@@ -29,42 +28,11 @@ FOV = 45.0
 CAM_A = ((1.8, 1.2, 5.0), (1.1, 0.6, 0.0))       # the box [-1, 1]^3 across the frame's left and lower edges
 CAM_B = ((-2.5, 0.4, 4.0), (-0.6, -0.8, 0.0))
 CAM_IN = ((0.2, 0.1, 0.3), (0.0, 0.0, -1.0))     # inside the box
-SETTLE = 14                                       # requests until a mask may take a buffer in use (kMissKeep) and more
-
-
-def gpu_scene(hs, skip):
-    old = os.environ.get("RT_MISS_SKIP")
-    os.environ["RT_MISS_SKIP"] = "1" if skip else "0"
-    try:
-        return rtm.GpuScene(hs, 0)
-    finally:
-        if old is None:
-            del os.environ["RT_MISS_SKIP"]
-        else:
-            os.environ["RT_MISS_SKIP"] = old
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("missmask") / "miss_mask_check")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", os.path.join(ROOT, "tests", "miss_mask_check.cpp"),
-                    "-o", exe], check=True)
-    return exe
-
-
-def cpu_mask(checker, path, W, H, spp, rect=None, cam=None):
-    """The CPU checker's counts for a scene file: {"items", "all_miss", "flagged", "flagged_with_hit"}."""
-    args = [checker, "scene", path, W, H, spp]
-    if rect is not None or cam is not None:
-        x0, y0, x1, y1 = rect or (0, 0, W, H)
-        args += [x0, y0, x1 - x0, y1 - y0]
-    if cam is not None:
-        args += [float(x).hex() for x in np.asarray(cam, np.float32)]
-    r = subprocess.run([str(a) for a in args], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    m = json.loads(r.stdout)["mask"]
-    assert m["flagged_with_hit"] == 0
-    return m
+    return build_checker(tmp_path_factory.mktemp("missmask"))
 
 
 @pytest.fixture(scope="module")
@@ -85,36 +53,6 @@ def synth(oracle, tmp_path_factory):
         a.close()
         b.close()
         hs.close()
-
-
-def cam16(cam):
-    return rtm.look_at(*cam) if cam is not None and len(cam) == 2 else cam
-
-
-def frame(gs, W, H, spp, cam=None, kernel=rtm.RT_KERNEL_AUTO):
-    f = gs.frame(W, H, spp, kernel=kernel)
-    c = cam16(cam)
-    if c is not None:
-        for k in range(16):
-            f.cam[k] = float(c[k])
-    return f
-
-
-def settled(render, gs):
-    """render() repeated until the frame's mask is in use for a second frame (or SETTLE frames): every repeat gives
-    the same result; returns (result, flagged items of the last frame)."""
-    first, flagged, used = None, 0, 0
-    for _ in range(SETTLE):
-        got = render()
-        if first is None:
-            first = got
-        for a, b in zip(first, got):
-            assert np.array_equal(a, b)
-        flagged = gs.miss_mask()[0]
-        used += flagged > 0
-        if used >= 2:
-            break
-    return first, flagged
 
 
 def four_ways(sc, W, H, spp, cam):
