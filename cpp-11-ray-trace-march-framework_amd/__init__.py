@@ -74,7 +74,7 @@ TRACER_SYMBOLS = [
     "rt_render_records_device", "rt_render_frame_host_tiled", "rt_fref_buffer_bytes",
     "rt_trace_rays_device", "rt_primary_rays_device", "rt_occluded_rays_device",
     "rt_ao_table", "rt_ao_rotations", "rt_render_ao_device", "rt_distance_points_device",
-    "rt_debug_miss_mask",
+    "rt_debug_miss_mask", "rt_debug_lane_launches",
 ]
 MAX_BATCH = 10                           # frames per rt_render_batch_device launch (kMaxBatch)
 
@@ -252,6 +252,8 @@ def tracer_lib():
         L.rt_debug_set_plan_delay.argtypes = [vp, c_u32]
         if hasattr(L, "rt_debug_miss_mask"):         # absent in earlier builds (A/B runs)
             L.rt_debug_miss_mask.argtypes = [vp, ctypes.POINTER(c_u32), ctypes.POINTER(c_u32)]
+        if hasattr(L, "rt_debug_lane_launches"):     # absent in earlier builds (A/B runs)
+            L.rt_debug_lane_launches.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         if hasattr(L, "rt_scene_set_timing"):
             L.rt_scene_set_timing.argtypes = [vp, c_u32]
         L.rt_sample_table.argtypes = [c_u32, vp]
@@ -737,6 +739,14 @@ class GpuScene:
         L = tracer_lib()
         a, b = c_u32(), c_u32()
         _check(L.rt_debug_miss_mask(self._h, ctypes.byref(a), ctypes.byref(b)), L, "rt_debug_miss_mask")
+        return a.value, b.value
+
+    def lane_launches(self):
+        """(lane-kernel launches this scene has led, those of them that ran as one-wave workgroups)
+        (rt_debug_lane_launches)."""
+        L = tracer_lib()
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(L.rt_debug_lane_launches(self._h, ctypes.byref(a), ctypes.byref(b)), L, "rt_debug_lane_launches")
         return a.value, b.value
 
     def last_kernel_ms(self):

@@ -34,59 +34,39 @@
 namespace rtk {
 namespace {
 
-// XCD-aware block order (kVarXcdBands).  The dispatcher deals workgroups round-robin to the 8
-// XCDs (block b runs on XCD b % 8), so consecutive blocks -- the 4 workgroups of one tile and
-// the tiles of one row -- land on 8 different L2s, and every XCD's L2 caches the whole visible
-// scene.  Remapped, XCD x takes turns of `chunk` consecutive blocks (one tile row): rows x,
-// x + 8, x + 16, ... -- compact rows for its L2, and the frame's cost still spread over all
-// XCDs.  chunk 0: one contiguous band per XCD (measured: load imbalance, up to 58 % slower).
-// A bijection on [0, nblocks) for any grid size (the tail past whole 8-turn rounds keeps its
-// order); on a device with another XCD count only the locality changes.
-__device__ __forceinline__ uint32_t xcd_band_block(uint32_t b, uint32_t nb, uint32_t chunk)
-{
-    if (chunk == 0u)
-    {
-        const uint32_t q = nb / kXcds, r = nb % kXcds;
-        const uint32_t x = b % kXcds, i = b / kXcds;
-        return x < r ? x * (q + 1u) + i : r * (q + 1u) + (x - r) * q + i;
-    }
-    const uint32_t full = nb / (kXcds * chunk) * (kXcds * chunk);
-    if (b >= full) return b;
-    const uint32_t x = b % kXcds, i = b / kXcds;
-    const uint32_t row = (i / chunk) * kXcds + x;
-    return row * chunk + i % chunk;
-}
+// (XCD-aware block order, kVarXcdBands: xcd_band_block in rt_kparams.h)
 
 // The launch's block -> block-of-work map.  With the heavy-first order on, blocks [0, hf_front)
 // take the blocks listed by the previous frame (in the order their heavy waves finished) and the
 // rest walk the natural (XCD-banded) order, skipping the listed blocks.  Returns false when this
-// block has nothing to do.  The marks read here are never written by this launch (the next
+// block has nothing to do.  The marks are never written by this launch (the next
 // frame's marks live in the other buffer), so every wave of a block decides alike.
-// lead: the first lane of launch block 0's first wave (unused since round 5: launch_plans clears the next plan).
+// mark: where the plan's mark of a block behind the front lies -- the block is skipped when the word equals hf_ver,
+// a test left to process_item, which loads the word beside the item's other prologue words -- or
+// null: no test (no front, no plan yet, or a block of the front).
+// (One copy of the band map serves both cases: hf_front is 0 without a front, and the host's xcd_full is that of the
+// nblk - hf_front lane blocks either way.)
 template <int VAR>
-__device__ __forceinline__ bool block_of_launch(const KParams& P, uint32_t& b, uint32_t bid, uint32_t nblk,
-                                                bool lead)
+__device__ __forceinline__ bool block_of_launch(const KParams& P, uint32_t& b, const uint32_t *& mark, uint32_t bid,
+                                                uint32_t nblk)
 {
     // (the next plan's counters are cleared by launch_plans right before k_hf_plan, not here: a
     // measured frame may run beside a frame that still reads the buffer it would clear)
-    (void)lead;
-    if (P.hf_front)
+    const uint32_t front = P.hf_front;
+    mark = nullptr;
+    if (bid < front)
     {
-        const uint32_t front = P.hf_front;
-        if (bid < front)
-        {
-            const uint32_t hi = min(P.hf_plan_in->cnt_hi, front);
-            const uint32_t lo = min(P.hf_plan_in->cnt_lo, front - hi);
-            if (bid >= hi && bid < front - lo) return false;
-            b = P.hf_list_in[bid];
-            return true;
-        }
-        const uint32_t q = bid - front;
-        const uint32_t nb = nblk - front;
-        b = (VAR & kVarXcdBands) ? xcd_band_block(q, nb, P.xcd_chunk) : q;
-        return P.hf_ver == 0u || P.hf_mark_in[b] != P.hf_ver;
+        // (the current plan's counts and list: wave-uniform words of a finished k_hf_plan, as the marks)
+        const uint32_t *plan = &P.hf_plan_in->cnt_hi;
+        const uint32_t hi = min(uniform_word(plan), front);
+        const uint32_t lo = min(uniform_word(plan + (offsetof(HfPlan, cnt_lo) / sizeof(uint32_t))), front - hi);
+        if (bid >= hi && bid < front - lo) return false;
+        b = uniform_word(P.hf_list_in + bid);
+        return true;
     }
-    b = (VAR & kVarXcdBands) ? xcd_band_block(bid, nblk, P.xcd_chunk) : bid;
+    const uint32_t q = bid - front;
+    b = (VAR & kVarXcdBands) ? xcd_band_block(q, nblk - front, P.xcd_chunk, P.xcd_chunk_m, P.xcd_full) : q;
+    if (front != 0u && P.hf_ver != 0u) mark = P.hf_mark_in + b;
     return true;
 }
 
@@ -418,14 +398,31 @@ __device__ __forceinline__ void wide_section_lds(const KParams& P, uint32_t wg)
     for (uint32_t li = wg - ng; li < n; li += nwg) wide_item_lds<BATCH, CLK>(P, li);
 }
 
+// The kernel arguments a lane wave's prologue reads -- the block map's, the item coordinates', the pointers of the
+// item's head -- and the camera's, asked for at the kernel's entry in ONE group of scalar loads with one wait
+// (DESIGN.md §4.33): left to the compiler, each is loaded in the basic block that first reads it, behind the early
+// exits, and waited for there (five waits in a row).  The empty asm only names the values; the later reads are
+// the same values, and all of them are dead before the walk.
+__device__ __forceinline__ void prologue_args(const KParams& P)
+{
+    asm volatile("" ::"s"(P.vblocks), "s"(P.xcd_full), "s"(P.hf_front), "s"(P.hf_ver), "s"(P.hf_measure),
+                 "s"(P.hf_mark_in), "s"(P.ipt_shift), "s"(P.tiles_x_m), "s"(P.xcd_chunk), "s"(P.xcd_chunk_m),
+                 "s"(P.spp), "s"(P.spp_shift), "s"(P.rx0), "s"(P.ry0), "s"(P.rw), "s"(P.rh), "s"(P.tiles_x),
+                 "s"(P.rank), "s"(P.nranks), "s"(P.tile_order), "s"(P.ndcx), "s"(P.ndcy), "s"(P.miss_mask));
+    asm volatile("" ::"s"(P.m[0]), "s"(P.m[1]), "s"(P.m[2]), "s"(P.m[3]), "s"(P.m[4]), "s"(P.m[5]), "s"(P.m[6]),
+                 "s"(P.m[7]), "s"(P.m[8]), "s"(P.org[0]), "s"(P.org[1]), "s"(P.org[2]));
+}
+
 // Wave `wib` (0-3) of launch block bid of nblk: its work item after the heavy-first / XCD-band map.
 template <int TRI, int VAR>
 __device__ __forceinline__ void lanes_block_wave(const KParams& P, uint32_t bid, uint32_t nblk, uint32_t wib,
                                                  volatile uint32_t *t0v)
 {
     uint32_t b;
-    if (!block_of_launch<VAR>(P, b, bid, nblk, bid == 0u && wib == 0u && (threadIdx.x & 63u) == 0u)) return;
-    const uint32_t item = b * kWavesPerWG + wib;
+    const uint32_t *mark;
+    if (!block_of_launch<VAR>(P, b, mark, bid, nblk)) return;
+    const uint32_t ver = P.hf_ver;
+    const uint32_t item = __builtin_amdgcn_readfirstlane(b * kWavesPerWG + wib);
     if constexpr ((VAR & kVarWideHeavy) != 0)
         if (P.wh_wgs && P.hf_ver && (P.wh_mark_in[item] & 0x7FFFFFFFu) == P.hf_ver) return;   // the wide section's
     if constexpr ((VAR & kVarWaveClock) != 0)
@@ -440,7 +437,9 @@ __device__ __forceinline__ void lanes_block_wave(const KParams& P, uint32_t bid,
         wave_lds_sync();
         const uint64_t r0 = __builtin_amdgcn_s_memrealtime();
         const uint64_t t0 = __builtin_amdgcn_s_memtime();
-        process_item<TRI, VAR>(P, item);
+        const ItemHead h = item_head<TRI, VAR>(P, item, mark);
+        if (mark && h.mark_w == ver) return;                              // the front's
+        process_item<TRI, VAR>(P, item, 0u, h);
         const uint64_t t1 = __builtin_amdgcn_s_memtime();
         const uint64_t r1 = __builtin_amdgcn_s_memrealtime();
         wave_lds_sync();
@@ -451,7 +450,9 @@ __device__ __forceinline__ void lanes_block_wave(const KParams& P, uint32_t bid,
     {
         const bool hf = P.hf_measure != 0u;
         if (hf && (threadIdx.x & 63u) == 0u) t0v[threadIdx.x >> 6] = uint32_t(__builtin_amdgcn_s_memtime());
-        process_item<TRI, VAR>(P, item);
+        const ItemHead h = item_head<TRI, VAR>(P, item, mark);
+        if (mark && h.mark_w == ver) return;                              // the front's: it stores the item's cost
+        process_item<TRI, VAR>(P, item, 0u, h);
         const KParams& Q = late_params(P);
         if (Q.hf_measure)
         {
@@ -469,6 +470,7 @@ __global__ void __launch_bounds__(kWG) k_render_lanes(KParams P)
 {
     __shared__ uint32_t t0s[kWavesPerWG];
     volatile uint32_t *t0v = t0s;                 // a wave's start time waits in LDS across the walk
+    prologue_args(P);
     lanes_block_wave<TRI, VAR>(P, blockIdx.x, gridDim.x, threadIdx.x >> 6, t0v);
 }
 
@@ -491,9 +493,10 @@ __global__ void __launch_bounds__(64) k_render_lanes_w64(KParams P)
     __shared__ uint32_t t0s[1];
     const uint32_t w = blockIdx.x, r = w / kXcds;
     const uint32_t vbid = (r >> 2) * kXcds + w % kXcds;
-    const KParams& Q = late_params(P);
-    if (vbid >= Q.vblocks) return;
-    lanes_block_wave<TRI, VAR>(P, vbid, Q.vblocks, r & 3u, t0s);
+    // (vblocks straight from P: one of the entry's group of argument loads, not a round trip of its own)
+    prologue_args(P);
+    if (vbid >= P.vblocks) return;
+    lanes_block_wave<TRI, VAR>(P, vbid, P.vblocks, r & 3u, t0s);
 }
 
 // kVarWideHeavy: the wide section, launched on the scene's side stream beside the lane kernel
@@ -523,13 +526,15 @@ __device__ __forceinline__ void batch_block_wave(const KBatch& B, uint32_t bid, 
                                                  volatile uint32_t *t0v)
 {
     uint32_t b;
-    if (!block_of_launch<VAR>(B.p[0], b, bid, nblk, bid == 0u && wib == 0u && (threadIdx.x & 63u) == 0u)) return;
+    const uint32_t *mark;
+    if (!block_of_launch<VAR>(B.p[0], b, mark, bid, nblk)) return;
+    const uint32_t ver = B.p[0].hf_ver;
     const uint32_t gitem = b * kWavesPerWG + wib;                    // launch-wide item
     if constexpr ((VAR & kVarWideHeavy) != 0)
         if (B.p[0].wh_wgs && B.p[0].hf_ver && (B.p[0].wh_mark_in[gitem] & 0x7FFFFFFFu) == B.p[0].hf_ver) return;
     const uint32_t f = batch_frame(B, b);
     const uint32_t off = uint32_t(offsetof(KBatch, p)) + f * uint32_t(sizeof(KParams));
-    const uint32_t item = gitem - B.base[f] * kWavesPerWG;
+    const uint32_t item = __builtin_amdgcn_readfirstlane(gitem - B.base[f] * kWavesPerWG);
     if constexpr ((VAR & kVarWaveClock) != 0)
     {
         // debug arm: the wave's clocks at its launch-wide item index (rt_debug_wave_clocks; the
@@ -543,7 +548,9 @@ __device__ __forceinline__ void batch_block_wave(const KBatch& B, uint32_t bid, 
         }
         wave_lds_sync();
         const uint64_t r0 = __builtin_amdgcn_s_memrealtime(), t0 = __builtin_amdgcn_s_memtime();
-        process_item<TRI, VAR>(late_params(B.p[0], off), item, off);
+        const ItemHead h = item_head<TRI, VAR>(late_params(B.p[0], off), item, mark);
+        if (mark && h.mark_w == ver) return;                              // the front's
+        process_item<TRI, VAR>(late_params(B.p[0], off), item, off, h);
         const uint64_t t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
         wave_lds_sync();
         const KParams& Q = late_params(B.p[0], uint32_t(offsetof(KBatch, p)));
@@ -557,7 +564,9 @@ __device__ __forceinline__ void batch_block_wave(const KBatch& B, uint32_t bid, 
     }
     const bool hf = B.p[0].hf_measure != 0u;
     if (hf && (threadIdx.x & 63u) == 0u) t0v[threadIdx.x >> 6] = uint32_t(__builtin_amdgcn_s_memtime());
-    process_item<TRI, VAR>(late_params(B.p[0], off), item, off);
+    const ItemHead h = item_head<TRI, VAR>(late_params(B.p[0], off), item, mark);
+    if (mark && h.mark_w == ver) return;                                  // the front's: it stores the item's cost
+    process_item<TRI, VAR>(late_params(B.p[0], off), item, off, h);
     const KParams& Q = late_params(B.p[0], uint32_t(offsetof(KBatch, p)));
     if (Q.hf_measure)
     {
@@ -635,7 +644,7 @@ __device__ __forceinline__ void batch_w64_body(const KBatch& B)
     }
     const uint32_t r = w / kXcds;
     const uint32_t vbid = (r >> 2) * kXcds + w % kXcds;
-    const uint32_t nv = late_params(B.p[0], uint32_t(offsetof(KBatch, p))).vblocks;
+    const uint32_t nv = B.p[0].vblocks;     // (one of the entry's group of argument loads)
     if (vbid >= nv) return;
     batch_block_wave<TRI, VAR>(B, vbid, nv, r & 3u, t0s);
 }

@@ -120,6 +120,8 @@ struct KParams
     uint32_t ipt_shift;         // lane kernels: log2 of the work items per tile (wg_per_tile * kWavesPerWG = 4 spp)
     uint32_t tiles_x_m;         // udiv_magic(tiles_x): the shard deal's t / tiles_x without a division
     uint32_t xcd_chunk;         // kVarXcdBands: consecutive blocks per XCD turn (0 = one band each)
+    uint32_t xcd_chunk_m;       // udiv_magic(xcd_chunk): xcd_band_block's i / chunk without a division
+    uint32_t xcd_full;          // xcd_band_full(the launch's lane blocks, xcd_chunk): blocks in whole 8-turn rounds
     uint32_t vblocks;           // k_render_lanes_w64: the 256-lane launch blocks its one-wave grid runs
     uint64_t *wave_clk;        // kVarWaveClock: {start, end, uniform tests, lane-loop iterations} per item
     const uint32_t *tile_order; // tile order (position -> local tile) or null = natural order
@@ -303,6 +305,29 @@ __host__ __device__ __forceinline__ void shard_tile_xy_m(uint32_t k, uint32_t ra
         udiv_by_magic(kShardRot * ty, tiles_x, tiles_x_m, r);
         tx = tx >= r ? tx - r : tx + tiles_x - r;
     }
+}
+
+// The XCD-band map (see kXcds above) without a runtime division: block b of the nb lane blocks of
+// a launch.  chunk and nb are the launch's, so the host passes chunk_m = udiv_magic(chunk) and full =
+// xcd_band_full(nb, chunk), the blocks in whole rounds of 8 turns; i / chunk and i % chunk come from
+// udiv_by_magic (exact for every i < 2^32).  chunk 0 divides by the constant 8 only.  Equal to
+//   full = nb / (8 chunk) * (8 chunk);  b >= full ? b : ((b / 8 / chunk) * 8 + b % 8) * chunk + b / 8 % chunk
+// for every b < nb (tests/block_map_check.cpp).
+inline uint32_t xcd_band_full(uint32_t nb, uint32_t chunk) { return chunk ? nb / (kXcds * chunk) * (kXcds * chunk) : 0u; }
+__host__ __device__ __forceinline__ uint32_t xcd_band_block(uint32_t b, uint32_t nb, uint32_t chunk, uint32_t chunk_m,
+                                                            uint32_t full)
+{
+    if (chunk == 0u)
+    {
+        const uint32_t q = nb / kXcds, r = nb % kXcds;
+        const uint32_t x = b % kXcds, i = b / kXcds;
+        return x < r ? x * (q + 1u) + i : r * (q + 1u) + (x - r) * q + i;
+    }
+    if (b >= full) return b;
+    const uint32_t x = b % kXcds, i = b / kXcds;
+    uint32_t in_turn;
+    const uint32_t turn = udiv_by_magic(i, chunk, chunk_m, in_turn);
+    return (turn * kXcds + x) * chunk + in_turn;
 }
 
 // The kernel table: rt_kernels.hip / rt_plan.hip hand the host code (rt_tracer.hip) the kernels it

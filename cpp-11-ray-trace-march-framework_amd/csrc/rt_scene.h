@@ -180,6 +180,8 @@ struct rt_scene
     uint64_t hf_evictions = 0;      // launch shapes that displaced another's state (rt_scene_info)
     uint64_t batch_launches = 0;    // rt_render_batch_device chunks led by this scene: one launch ...
     uint64_t batch_fallbacks = 0;   // ... or one launch per frame (frames that cannot share a launch)
+    uint64_t lane_launches = 0;     // rt_debug_lane_launches: lane-kernel launches led by this scene (single frames
+    uint64_t w64_launches = 0;      // and batches), and those of them that ran as one-wave workgroups
     // scheduling tunables, read ONCE from the environment at rt_scene_create (A/B sweeps): the
     // launch path never calls getenv
     uint32_t hf_floor = 100000;     // RT_HF_FLOOR: heavy-first threshold floor, shader cycles
@@ -199,7 +201,7 @@ struct rt_scene
     uint32_t wh_auto_refs = 128;    // RT_WH_AUTO_REFS: AUTO takes the wide section for >= 2-rank
                                     // shards of scenes with a cell list this long
     uint32_t wg64 = 1;              // RT_WG64: AUTO launches of >= wg64_min_blocks 256-lane blocks run
-    uint32_t wg64_min_blocks = 8192; // as one-wave workgroups (k_render_lanes_w64)
+    uint32_t wg64_min_blocks = 8192; // as one-wave workgroups (k_render_lanes_w64); RT_WG64_MIN_BLOCKS
     uint32_t wg64_batch_min_blocks = 0;  // the same for batched launches
     uint32_t wg64_max_refs = 1024;  // RT_WG64_MAX_REFS: single-frame launches of scenes with a cell of this many
                                     // references keep 256-lane workgroups

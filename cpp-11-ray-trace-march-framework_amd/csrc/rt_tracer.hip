@@ -720,6 +720,10 @@ int launch_render(rt_scene *s, const rt_frame *f, KParams& P, uint32_t n_local_t
     // whole rows interleave over the XCDs, so each L2 sees compact rows AND the frame's cost
     // spreads evenly (half rows put every left half on the even XCDs).
     P.xcd_chunk = ((P.tiles_x + P.nranks - 1u) / P.nranks) * P.wg_per_tile;
+    // ... and the band map's two quotients, once per launch (xcd_band_block): the launch's lane blocks are `blocks`
+    // with a front (the grid's hf_front blocks more lead it) and without one
+    P.xcd_chunk_m = udiv_magic(P.xcd_chunk);
+    P.xcd_full = xcd_band_full(uint32_t(blocks), P.xcd_chunk);
     // AUTO (and the COMPACT arm built on its per-ray code): the feature set of kVarAuto that this
     // scene allows -- the Newton reciprocal needs rcp_safe, the packed counts and the empty-run
     // loop need pack_ok.  DESIGN.md §4.1 has the measured progression.
@@ -844,7 +848,9 @@ int launch_render(rt_scene *s, const rt_frame *f, KParams& P, uint32_t n_local_t
             P.vblocks = grid;
             lgrid = kWavesPerWG * ((grid + kXcds - 1u) / kXcds * kXcds);
             lwg = 64u;
+            s->w64_launches++;
         }
+        s->lane_launches++;
         if (P.wh_wgs)
         {
             RT_HIP(mark(kt0));
@@ -1007,6 +1013,9 @@ int launch_batch(rt_scene *const *S, const rt_frame *F, uint32_t n, KParams *P, 
         P[i].ipt_shift = log2u(wgpt * kWavesPerWG);
         P[i].tiles_x_m = udiv_magic(P[i].tiles_x);
         P[i].xcd_chunk = ((P[i].tiles_x + P[i].nranks - 1u) / P[i].nranks) * wgpt;
+        // (the batch kernel maps the launch's blocks -- every frame's -- by P[0]'s three band fields)
+        P[i].xcd_chunk_m = udiv_magic(P[i].xcd_chunk);
+        P[i].xcd_full = xcd_band_full(uint32_t(blocks), P[i].xcd_chunk);
     }
     // RT_KERNEL_FLAG_OVERLAP (every frame of the batch): this launch may run beside the scenes' last
     // launch on another stream -- its tail under this launch's start -- when no scene state changes
@@ -1095,7 +1104,9 @@ int launch_batch(rt_scene *const *S, const rt_frame *F, uint32_t n, KParams *P, 
         P[0].vblocks = uint32_t(blocks) + P[0].hf_front;
         grid = kWavesPerWG * ((fused ? P[0].wh_wgs : 0u) + (P[0].vblocks + kXcds - 1u) / kXcds * kXcds);
         bwg = 64u;
+        s0->w64_launches++;
     }
+    s0->lane_launches++;
     // the fused one-wave kernel held to 8 waves / SIMD (76 SGPRs; the plain build's 83 admit 7), per
     // rank count (wg64_o8, bit log2 N): a rank of 2 0.2925 vs 0.3025 ms, of 8 0.1171-0.1182 vs
     // 0.1139-0.1151 (profiles/r05f_ab_o8.json), so 2 only
@@ -1330,6 +1341,7 @@ int rt_scene_create(const rt_scene_desc *d, int device, rt_scene **out)
     // scheduling tunables: read once here, never per launch (A/B sweeps set them per scene)
     s->hf_floor = env_tunable("RT_HF_FLOOR", s->hf_floor);
     s->hf_min_blocks = env_tunable("RT_HF_MIN_BLOCKS", s->hf_min_blocks);
+    s->wg64_min_blocks = env_tunable("RT_WG64_MIN_BLOCKS", s->wg64_min_blocks);   // (tests: small frames on k_render_lanes_w64)
     s->hf_shift = std::min(env_tunable("RT_HF_SHIFT", s->hf_shift), 8u);
     s->hf_pos16 = std::min(env_tunable("RT_HF_POS16", s->hf_pos16), 64u);
     s->wg64 = env_tunable("RT_WG64", s->wg64);
@@ -2614,6 +2626,15 @@ int rt_debug_miss_mask(rt_scene *s, uint32_t *flagged, uint32_t *computed)
     const int b = s->miss_frame_slot;
     *flagged = b >= 0 ? (*static_cast<volatile uint32_t *>(s->h_miss_cnt + b) & 0x00FFFFFFu) : 0u;
     *computed = s->miss_computed;
+    return RT_OK;
+}
+
+int rt_debug_lane_launches(rt_scene *s, uint64_t *launches, uint64_t *one_wave)
+{
+    if (!s || !launches || !one_wave) return fail(RT_E_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    *launches = s->lane_launches;
+    *one_wave = s->w64_launches;
     return RT_OK;
 }
 

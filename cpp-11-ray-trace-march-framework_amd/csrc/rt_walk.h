@@ -1318,13 +1318,14 @@ __device__ __forceinline__ float miss_colour(uint32_t py, uint32_t H) { return f
 
 // renderer.cpp:88-122: one sample -> its colour contribution; hit_tri = the hit triangle
 // (Grid::Intersect's tri_idx, renderer.cpp:105) or kNoTri
+// (trace_sample_at: from the sample's camera-space x, y -- KParams::ndcx / ndcy entries the caller has loaded)
 template <bool STATS, int TRI, int VAR>
-__device__ __forceinline__ void trace_sample(const KParams& P, uint32_t px, uint32_t py, uint32_t s, float& cr,
-                                             float& cg, float& cb, uint32_t& hit_tri, rt_sample_rec *rec,
-                                             uint32_t off = 0u, SampleOut *so = nullptr)
+__device__ __forceinline__ void trace_sample_at(const KParams& P, float cam_x, float cam_y, uint32_t py, float& cr,
+                                                float& cg, float& cb, uint32_t& hit_tri, rt_sample_rec *rec,
+                                                uint32_t off = 0u, SampleOut *so = nullptr)
 {
     float dx, dy, dz;
-    rtd::dir_from_xy(P.m, P.ndcx[px * P.spp + s], P.ndcy[py * P.spp + s], dx, dy, dz);    // camera.h:8-47
+    rtd::dir_from_xy(P.m, cam_x, cam_y, dx, dy, dz);                                       // camera.h:8-47
     float t = 0.0f, u = 0.0f, v = 0.0f;
     uint32_t tri = rtd::kNoTri, voxel = rtd::kNoTri, steps = 0, tests = 0;
     bool hit;
@@ -1379,6 +1380,15 @@ __device__ __forceinline__ void trace_sample(const KParams& P, uint32_t px, uint
         rec->r = cr; rec->g = cg; rec->b = cb;
         rec->pad = 0;
     }
+}
+
+template <bool STATS, int TRI, int VAR>
+__device__ __forceinline__ void trace_sample(const KParams& P, uint32_t px, uint32_t py, uint32_t s, float& cr,
+                                             float& cg, float& cb, uint32_t& hit_tri, rt_sample_rec *rec,
+                                             uint32_t off = 0u, SampleOut *so = nullptr)
+{
+    trace_sample_at<STATS, TRI, VAR>(P, P.ndcx[px * P.spp + s], P.ndcy[py * P.spp + s], py, cr, cg, cb, hit_tri, rec,
+                                     off, so);
 }
 
 // Tile bookkeeping: block -> (local tile k, sub-block)
@@ -1490,11 +1500,23 @@ __device__ __forceinline__ ItemCoord item_coord_pre(const KParams& P, uint32_t i
 
 // The miss skip: bit `local tile k * items per tile + item in tile` of KParams::miss_mask -- the
 // launch's NATURAL item order, whatever tile_order says -- is set when k_miss_mask proved that every sample of
-// the item misses the grid box (rt_miss_mask.h).  Wave-uniform: one scalar load and a bit test.
-__device__ __forceinline__ bool item_flagged(const KParams& P, uint32_t item, uint32_t k)
+// the item misses the grid box (rt_miss_mask.h).  Wave-uniform: one scalar load (process_item issues it beside the
+// item's other prologue words) and a bit test.
+__device__ __forceinline__ uint32_t item_flag_index(const KParams& P, uint32_t item, uint32_t k)
 {
-    const uint32_t idx = (k << P.ipt_shift) + (item & ((1u << P.ipt_shift) - 1u));
-    return ((P.miss_mask[idx >> 5] >> (idx & 31u)) & 1u) != 0u;
+    return (k << P.ipt_shift) + (item & ((1u << P.ipt_shift) - 1u));
+}
+
+// A wave-uniform word read through the scalar cache (words a kernel wrote and finished before this
+// one was dispatched -- the plan's marks, the miss mask -- as the per-origin records of test_cell are read).
+__device__ __forceinline__ uint32_t uniform_word(const uint32_t *p)
+{
+    return *(const __attribute__((address_space(4))) uint32_t *)(uint64_t(p));
+}
+// ... and a word that can always be read, for the loads of a group that have nothing to fetch: the kernel's arguments
+__device__ __forceinline__ const uint32_t *spare_word()
+{
+    return (const uint32_t *)uint64_t(__builtin_amdgcn_kernarg_segment_ptr());
 }
 
 // The resolve of one pixel (renderer.cpp:124-133), shared by process_item and k_miss_mask's row table.
@@ -1563,29 +1585,56 @@ __device__ __forceinline__ void process_record(const KParams& Q, const ItemCoord
 // (a 2^k x 2^k pixel block x spp samples).  Traces the lane's sample, sums the pixel's
 // samples across its adjacent lanes in sample order (renderer.cpp:87-122, hazard H10) and
 // stores the packed pixel (renderer.cpp:124-133).
+//
+// The item's head (item_head) is everything its prologue reads from memory, sent out as ONE group:
+// the plan mark of the item's block (block_of_launch; the caller tests it) and the miss-mask word -- wave-uniform:
+// scalar loads -- and the lane's two camera-space table entries.  None of the four addresses depends on another's
+// value, so all are issued before the first test that reads one and waited for once.  A load with nothing to fetch
+// reads a spare word (no mark, no mask) or entry 0 of its table (a lane outside the region), so every address is in
+// bounds for every launched block; the tests then read what has arrived, in the order they always had.
+struct ItemHead { ItemCoord ic; uint32_t mark_w, mask_w, flag; float cam_x, cam_y; };
+
+// the miss skip (AUTO's lane kernels on the grid walk; the host passes a mask only to frames without hit
+// IDs or records): a flagged item's pixels take the row's all-miss word, and no ray is generated
 template <int TRI, int VAR>
-__device__ __forceinline__ void process_item(const KParams& P, uint32_t item, uint32_t off = 0u)
+constexpr bool kItemMissSkip = TRI == RT_TRI_MOLLER_TRUMBORE && (VAR & kVarAutoCore) == kVarAutoCore &&
+                               (VAR & (kVarWaveClock | kVarLdsSplit | kVarMarch | kVarBrute | kVarRays)) == 0;
+
+// item: wave-uniform (readfirstlane'd by the caller); mark: the block's plan mark, or null
+template <int TRI, int VAR>
+__device__ __forceinline__ ItemHead item_head(const KParams& P, uint32_t item, const uint32_t *mark = nullptr)
 {
-    item = __builtin_amdgcn_readfirstlane(item);
+    ItemHead h;
+    h.ic = item_coord_pre(P, item, threadIdx.x & 63u);
+    const ItemCoord& ic = h.ic;
+    h.flag = kItemMissSkip<TRI, VAR> ? item_flag_index(P, item, ic.c.k) : 0u;
+    h.mark_w = uniform_word(mark ? mark : spare_word());
+    h.mask_w = kItemMissSkip<TRI, VAR> ? uniform_word(P.miss_mask ? P.miss_mask + (h.flag >> 5) : spare_word()) : 0u;
+    h.cam_x = P.ndcx[ic.valid ? ic.x * P.spp + ic.s : 0u];
+    h.cam_y = P.ndcy[ic.valid ? ic.y * P.spp + ic.s : 0u];
+    asm volatile("" : "+s"(h.mark_w), "+s"(h.mask_w), "+v"(h.cam_x), "+v"(h.cam_y));     // the group's one wait
+    return h;
+}
+
+template <int TRI, int VAR>
+__device__ __forceinline__ void process_item(const KParams& P, uint32_t item, uint32_t off, const ItemHead& h)
+{
     const uint32_t lane = threadIdx.x & 63u;
     float cr = 0.0f, cg = 0.0f, cb = 0.0f;
     uint32_t hit_tri = rtd::kNoTri;
     SampleOut so{false, 0.0f, 0.0f, 0.0f, rtd::kNoTri, rtd::kNoTri};
     uint32_t origin;
     {
-        const ItemCoord ic = item_coord_pre(P, item, lane);
-        // the miss skip (AUTO's lane kernels on the grid walk; the host passes a mask only to frames without hit
-        // IDs or records): a flagged item's pixels take the row's all-miss word, and no ray is generated
-        if constexpr (TRI == RT_TRI_MOLLER_TRUMBORE && (VAR & kVarAutoCore) == kVarAutoCore &&
-                      (VAR & (kVarWaveClock | kVarLdsSplit | kVarMarch | kVarBrute | kVarRays)) == 0)
-            if (P.miss_mask && item_flagged(P, item, ic.c.k))
+        const ItemCoord& ic = h.ic;
+        if constexpr (kItemMissSkip<TRI, VAR>)
+            if (P.miss_mask && ((h.mask_w >> (h.flag & 31u)) & 1u) != 0u)
             {
                 if (ic.valid && ic.s == 0) store_pixel(P, ic.c, ic.p, ic.x, ic.y, P.rowmiss[ic.y]);
                 return;
             }
         origin = tile_origin_word(ic);
         if (ic.valid)
-            trace_sample<false, TRI, VAR>(P, ic.x, ic.y, ic.s, cr, cg, cb, hit_tri, nullptr, off, &so);
+            trace_sample_at<false, TRI, VAR>(P, h.cam_x, h.cam_y, ic.y, cr, cg, cb, hit_tri, nullptr, off, &so);
     }
     const KParams& Q = late_params(P, off);
     const ItemCoord ic = item_coord_post(Q, item, lane, origin);
@@ -1633,6 +1682,14 @@ __device__ __forceinline__ void process_item(const KParams& P, uint32_t item, ui
     {
         store_pixel(Q, ic.c, ic.p, ic.x, ic.y, resolve_word(Q, sr, sg, sb));
     }
+}
+
+// an item with no plan mark to test (the wide section's LDS tier)
+template <int TRI, int VAR>
+__device__ __forceinline__ void process_item(const KParams& P, uint32_t item, uint32_t off = 0u)
+{
+    item = __builtin_amdgcn_readfirstlane(item);
+    process_item<TRI, VAR>(P, item, off, item_head<TRI, VAR>(P, item));
 }
 
 } // namespace

@@ -541,6 +541,10 @@ int rt_debug_wide_tiers(rt_scene *s, uint32_t *listed, uint32_t *lds);
    shard, two of them per scene).  Synchronises the device. */
 int rt_debug_miss_mask(rt_scene *s, uint32_t *flagged, uint32_t *computed);
 
+/* Tests: lane-kernel launches this scene has led so far (single frames, shards and batches), and how many of
+   them ran as one-wave workgroups (k_render_lanes_w64 / k_render_batch_w64: RT_WG64, RT_WG64_MIN_BLOCKS). */
+int rt_debug_lane_launches(rt_scene *s, uint64_t *launches, uint64_t *one_wave);
+
 /* What rt_scene_create chose for a scene, and the scheduling tunables it read once from the
    environment (RT_HF_FLOOR, RT_HF_MIN_BLOCKS, RT_WH_FLOOR, RT_WH_ALPHA16, RT_WH_ALPHA16_N2,
    RT_WH_AUTO_REFS, RT_WH_LDS, ...): never re-read per launch. */
