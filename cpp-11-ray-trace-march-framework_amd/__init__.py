@@ -27,7 +27,7 @@ KERNEL_SOURCES = ("csrc/rt_kernels.hip", "csrc/rt_walk.h", "csrc/rt_kparams.h", 
                   "csrc/rt_scene.h", "csrc/rt_tracer.hip", "csrc/rt_grid_build.hip", "csrc/rt_device.h",
                   "csrc/rt_internal.h", "csrc/rt_box_words.h", "csrc/rt_fref_slots.h", "csrc/rt_cam_bound.h", "csrc/rt_record_gate.h", "csrc/rt_setup_div.h", "csrc/rt_miss_mask.h", "csrc/rt_rays.hip",
                   "csrc/rt_ray_common.h", "csrc/rt_occlusion.hip", "csrc/rt_ao.hip", "csrc/rt_distance.hip",
-                  "csrc/rt_dist_tree.h", "csrc/Makefile",
+                  "csrc/rt_dist_tree.h", "csrc/rt_launch.hip", "csrc/rt_queries.hip", "csrc/rt_launch.h", "csrc/Makefile",
                   "../include/rt_tracer.h")
 
 

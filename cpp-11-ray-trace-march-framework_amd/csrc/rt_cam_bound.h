@@ -1,7 +1,7 @@
 // rt_cam_bound.h -- how long a camera ray's direction components can be, from the frame's 3x3 alone.
 //
 // Host only, plain float / double: librt_tracer.so calls it once per frame where it picks the frame's
-// traversal features (rt_tracer.hip: frame_gated, frame_traversal_bits), and tests/record_gate_check.cpp compiles the same
+// traversal features (rt_launch.hip: frame_gated, frame_traversal_bits), and tests/record_gate_check.cpp compiles the same
 // function, so the library and the checker cannot disagree about which cameras keep the record gate.
 //
 // rt_frame.cam is the caller's matrix and need not be orthonormal.  rtd::dir_from_xy (camera.h:39-46)

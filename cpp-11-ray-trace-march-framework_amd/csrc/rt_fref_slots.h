@@ -1,5 +1,5 @@
 // rt_fref_slots.h -- which of a scene's two per-camera-origin record buffers (rt_scene::d_frefs) a frame
-// reads, and when a buffer may be recomputed.  Host only, no HIP, C++11: rt_tracer.hip
+// reads, and when a buffer may be recomputed.  Host only, no HIP, C++11: rt_launch.hip
 // runs these functions and tests/fref_slot_check.cpp checks the same ones exhaustively on the CPU.
 #pragma once
 #include <cstdint>

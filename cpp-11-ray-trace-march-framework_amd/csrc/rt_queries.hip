@@ -1,0 +1,358 @@
+// rt_queries.hip -- the query entry points of librt_tracer.so (include/rt_tracer.h): per-sample records of a frame
+// rectangle (rt_trace_samples), caller-supplied rays (rt_trace_rays_device), occlusion (rt_occluded_rays_device),
+// point distances (rt_distance_points_device), a frame's primary rays (rt_primary_rays_device) and AO frames
+// (rt_render_ao_device).  Kernels: rt_kernels.hip, rt_rays.hip, rt_occlusion.hip, rt_distance.hip, rt_ao.hip.
+// What they share with the render launches (rt_launch.hip) is declared in rt_launch.h.
+
+#include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <string>
+
+#include "../../include/rt_tracer.h"
+#include "rt_device.h"
+#include "rt_launch.h"
+
+using namespace rtk;
+
+namespace {
+// The parameters of a query: the scene's arrays and grid constants as rt_scene_create wrote them -- with a frame
+// (AO), the frame's too -- and no per-camera-origin state, which is not these paths'
+void query_params(const rt_scene *s, KParams& P, const rt_frame *f = nullptr)
+{
+    if (f)
+        frame_params(s, f, P);
+    else
+    {
+        std::memset(&P, 0, sizeof(P));
+        scene_params(s, P);
+    }
+    P.frefs = nullptr;
+    P.gates = nullptr;
+}
+
+// RT_RAYS_SORT / RT_DIST_SORT, under the scene's mutex: the caller fills *keys with its sort words on st
+// (sorted_begin), the grid build's radix sort orders them by their low `bits` bits (sorted_finish), and *sorted is
+// the order the query kernel then reads its input through.  The scratch is the scene's and is the one piece of
+// state the queries have: sorted calls are serialised by the scene's mutex, and one on another stream than the
+// last waits for it (rays_ev).  It grows -- a free and an allocation, which wait for the device -- only when
+// n exceeds every earlier sorted n.  rays_sorted_done, after the kernel's launch, marks the scratch's last use.
+int sorted_begin(rt_scene *s, hipStream_t st, uint32_t n, unsigned long long **keys)
+{
+    if (!s->rays_ev) RT_HIP(hipEventCreateWithFlags(&s->rays_ev, s->ev_order_flags));
+    if (s->rays_ev_recorded && st != s->rays_stream) RT_HIP(hipStreamWaitEvent(st, s->rays_ev, 0));
+    return rt_internal_sort_reserve(&s->rays_sort, n, keys);
+}
+
+int sorted_finish(rt_scene *s, hipStream_t st, uint32_t n, uint32_t bits, unsigned long long **sorted)
+{
+    return rt_internal_sort_run(s->rays_sort, st, n, bits, sorted);
+}
+
+// The ray queries' sorted order: sort words of k_ray_keys
+int rays_sorted_order(rt_scene *s, const KParams& P, const float2 *rays, uint32_t n, hipStream_t st,
+                      unsigned long long **sorted)
+{
+    unsigned long long *keys = nullptr;
+    if (int rc = sorted_begin(s, st, n, &keys)) return rc;
+    // cells per axis beyond 512 drop their low bits from the key (9 bits an axis)
+    uint32_t shift = 0;
+    while ((std::max(std::max(s->dims[0], s->dims[1]), s->dims[2]) - 1u) >> shift >= 512u) shift++;
+    hipLaunchKernelGGL(ray_keys_kernel(), dim3((n + kWG - 1) / kWG), dim3(kWG), 0, st, P, rays, n, shift, keys);
+    RT_HIP(hipGetLastError());
+    return sorted_finish(s, st, n, ray_key_bits(), sorted);
+}
+
+int rays_sorted_done(rt_scene *s, hipStream_t st)
+{
+    RT_HIP(hipEventRecord(s->rays_ev, st));
+    s->rays_stream = st;
+    s->rays_ev_recorded = true;
+    return RT_OK;
+}
+} // namespace
+
+extern "C" {
+
+int rt_trace_samples(rt_scene *s, const rt_frame *f, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                     rt_sample_rec *out)
+{
+    if (!s || !out) return fail(RT_E_INVALID, "NULL argument");
+    int rc = validate_frame(f);
+    if (rc) return rc;
+    if (w == 0 || h == 0 || x0 + w > f->width || y0 + h > f->height)
+        return fail(RT_E_INVALID, "rectangle outside the frame");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if ((rc = ensure_device(s))) return rc;
+    const uint32_t spp = std::max(1u, f->spp);
+    if ((rc = prepare_samples(s, f, spp))) return rc;
+    const uint64_t n64 = uint64_t(w) * h * spp;
+    if (n64 > (1ull << 28)) return fail(RT_E_INVALID, "too many samples for one record call");
+    const uint32_t n = uint32_t(n64);
+    rt_sample_rec *d_rec = nullptr;
+    RT_HIP(hipMalloc(&d_rec, sizeof(rt_sample_rec) * n));
+    KParams P;
+    frame_params(s, f, P);
+    set_records(P, RecOut{ d_rec, x0, y0, w, h });
+    if (P.isect == RT_ISECT_RAY_MARCH && (f->kernel & RT_KERNEL_FLAG_EXHAUSTIVE)) P.isect += 0x100;
+    if ((rc = flush_tables(s, s->stream)))
+    {
+        (void)hipFree(d_rec);
+        return rc;
+    }
+    hipLaunchKernelGGL(trace_records_kernel(), dim3((n + kWG - 1) / kWG), dim3(kWG), 0, s->stream, P, n);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_rec, sizeof(rt_sample_rec) * n, hipMemcpyDeviceToHost, s->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    (void)hipFree(d_rec);
+    if (e != hipSuccess) return fail(RT_E_HIP, std::string("rt_trace_samples: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
+// Every argument is checked before the scene is touched.  Without RT_RAYS_SORT no lock and no events: the
+// launch reads only what rt_scene_create wrote (scene_params), so it is ordered against nothing but its
+// own stream.
+int rt_trace_rays_device(rt_scene *s, const rt_ray *d_rays, uint32_t n, uint32_t flags, rt_ray_hit *d_hits,
+                         rt_sample_rec *d_recs, void *hip_stream)
+{
+    if (!s) return fail(RT_E_INVALID, "scene is NULL");
+    if (flags & ~uint32_t(RT_RAYS_COUNT | RT_RAYS_SORT)) return fail(RT_E_INVALID, "unknown rt_rays_flags bit");
+    const bool count = (flags & RT_RAYS_COUNT) != 0u, sort = (flags & RT_RAYS_SORT) != 0u;
+    if (count && !d_recs) return fail(RT_E_INVALID, "RT_RAYS_COUNT needs d_recs");
+    if (!count && d_recs) return fail(RT_E_INVALID, "d_recs without RT_RAYS_COUNT");
+    if (n >= 0x80000000u) return fail(RT_E_INVALID, "n must be below 2^31");
+    if (n == 0) return RT_OK;
+    if (!d_rays) return fail(RT_E_INVALID, "d_rays is NULL");
+    if (!count && !d_hits) return fail(RT_E_INVALID, "d_hits is NULL");
+    if ((uintptr_t(d_rays) | uintptr_t(d_hits) | uintptr_t(d_recs)) & 7u)
+        return fail(RT_E_INVALID, "d_rays, d_hits and d_recs must be 8-byte aligned");
+    if (int rc = ensure_device(s)) return rc;
+    KParams P;
+    query_params(s, P);
+    // the fast arm's walk: the box runs where the scene has them, else the octant distance skip (a scene
+    // without packed cell words walks the plain CSR ranges: grid_intersect tests P.cellw)
+    const int var = kVarRays | kVarWaveGate | kVarDistSkip | scene_traversal_bits(s);
+    const rays_fn fn = trace_rays_kernel(var, count);
+    if (!fn) return fail(RT_E_INVALID, "kernel variant not built: " + std::to_string(var));
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const float2 *rays = reinterpret_cast<const float2 *>(d_rays);
+    const dim3 grid((n + kWG - 1) / kWG), wg(kWG);
+    if (!sort)
+    {
+        hipLaunchKernelGGL(fn, grid, wg, 0, st, P, rays, static_cast<const unsigned long long *>(nullptr), n, d_hits,
+                           d_recs);
+        RT_HIP(hipGetLastError());
+        return RT_OK;
+    }
+    // RT_RAYS_SORT: the same trace kernel reading its rays through the sorted words (rays_sorted_order)
+    std::lock_guard<std::mutex> lk(s->mtx);
+    unsigned long long *sorted = nullptr;
+    if (int rc = rays_sorted_order(s, P, rays, n, st, &sorted)) return rc;
+    hipLaunchKernelGGL(fn, grid, wg, 0, st, P, rays, static_cast<const unsigned long long *>(sorted), n, d_hits, d_recs);
+    RT_HIP(hipGetLastError());
+    return rays_sorted_done(s, st);
+}
+
+// Ray i is occluded iff the any-hit walk over (tmin, tmax) finds a test that counts (include/rt_tracer.h).  The
+// argument rules, the variant table, the sort path and the absence of state without RT_RAYS_SORT are
+// rt_trace_rays_device's.
+int rt_occluded_rays_device(rt_scene *s, const rt_ray *d_rays, const float *d_tminmax, uint32_t n, uint32_t flags,
+                            uint8_t *d_occluded, void *hip_stream)
+{
+    if (!s) return fail(RT_E_INVALID, "scene is NULL");
+    if (flags & RT_RAYS_COUNT) return fail(RT_E_INVALID, "RT_RAYS_COUNT: the occlusion walk has no counting arm");
+    if (flags & ~uint32_t(RT_RAYS_SORT)) return fail(RT_E_INVALID, "unknown rt_rays_flags bit");
+    const bool sort = (flags & RT_RAYS_SORT) != 0u;
+    if (n >= 0x80000000u) return fail(RT_E_INVALID, "n must be below 2^31");
+    if (n == 0) return RT_OK;
+    if (!d_rays) return fail(RT_E_INVALID, "d_rays is NULL");
+    if (!d_occluded) return fail(RT_E_INVALID, "d_occluded is NULL");
+    if ((uintptr_t(d_rays) | uintptr_t(d_tminmax)) & 7u)
+        return fail(RT_E_INVALID, "d_rays and d_tminmax must be 8-byte aligned");
+    if (int rc = ensure_device(s)) return rc;
+    KParams P;
+    query_params(s, P);
+    const int var = kVarAnyHit | kVarRays | kVarWaveGate | kVarDistSkip | scene_traversal_bits(s);
+    const occluded_fn fn = occluded_rays_kernel(var);
+    if (!fn) return fail(RT_E_INVALID, "kernel variant not built: " + std::to_string(var));
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const float2 *rays = reinterpret_cast<const float2 *>(d_rays);
+    const float2 *tmm = reinterpret_cast<const float2 *>(d_tminmax);
+    const dim3 grid((n + kWG - 1) / kWG), wg(kWG);
+    if (!sort)
+    {
+        hipLaunchKernelGGL(fn, grid, wg, 0, st, P, rays, tmm, static_cast<const unsigned long long *>(nullptr), n,
+                           d_occluded);
+        RT_HIP(hipGetLastError());
+        return RT_OK;
+    }
+    std::lock_guard<std::mutex> lk(s->mtx);
+    unsigned long long *sorted = nullptr;
+    if (int rc = rays_sorted_order(s, P, rays, n, st, &sorted)) return rc;
+    hipLaunchKernelGGL(fn, grid, wg, 0, st, P, rays, tmm, static_cast<const unsigned long long *>(sorted), n, d_occluded);
+    RT_HIP(hipGetLastError());
+    return rays_sorted_done(s, st);
+}
+
+// DistanceBruteForce for caller-supplied points (include/rt_tracer.h; kernels: rt_distance.hip).  The argument rules,
+// the sort path (the scene's sort scratch and its event, shared with the ray queries) and the absence of state
+// without RT_DIST_SORT are rt_trace_rays_device's.
+int rt_distance_points_device(rt_scene *s, const float *d_points, uint32_t n, uint32_t flags, rt_point_dist *d_out,
+                              float *d_closest, void *hip_stream)
+{
+    if (!s) return fail(RT_E_INVALID, "scene is NULL");
+    if (flags & ~uint32_t(RT_DIST_EXHAUSTIVE | RT_DIST_SORT)) return fail(RT_E_INVALID, "unknown rt_dist_flags bit");
+    if (n >= 0x80000000u) return fail(RT_E_INVALID, "n must be below 2^31");
+    if (n == 0) return RT_OK;
+    if (!d_points) return fail(RT_E_INVALID, "d_points is NULL");
+    if (!d_out) return fail(RT_E_INVALID, "d_out is NULL");
+    if ((uintptr_t(d_points) | uintptr_t(d_closest)) & 3u)
+        return fail(RT_E_INVALID, "d_points and d_closest must be 4-byte aligned");
+    if (uintptr_t(d_out) & 7u) return fail(RT_E_INVALID, "d_out must be 8-byte aligned");
+    if (int rc = ensure_device(s)) return rc;
+    KDist D;
+    std::memset(&D, 0, sizeof(D));
+    D.tri_dist = s->d_tridist;
+    D.tri_idx = s->d_distidx;
+    D.blk = s->d_distblk;
+    D.blk_key = s->d_distkey;
+    D.nodes = s->d_distnodes;
+    D.ntris = s->ntris;
+    D.nblk = s->ndist_blk;
+    D.nlevels = s->dist_levels;
+    for (uint32_t l = 0; l < kDistLevels; l++)
+    {
+        D.lvl_off[l] = s->dist_lvl_off[l];
+        D.lvl_n[l] = s->dist_lvl_n[l];
+    }
+    D.scene_scale = s->scene_scale;
+    for (int a = 0; a < 3; a++)
+    {
+        const float ext = s->vmax[a] - s->vmin[a];
+        D.vmin[a] = s->vmin[a];
+        D.vinv[a] = ext > 0.0f && 1024.0f / ext <= rtd::kFltMax ? 1024.0f / ext : 0.0f;
+    }
+    D.points = d_points;
+    D.n = n;
+    D.out = reinterpret_cast<uint2 *>(d_out);
+    D.closest = d_closest;
+    // A mesh of at most two blocks (64 triangles) takes the exhaustive kernel in the default arm too: the seed alone
+    // is half or all of such a mesh, so the cull can only add its own cost (scene 1, 44 triangles: 0.35 ms against
+    // 0.20 ms for 1.4 M points, profiles/distance_bench.json).  Same bytes either way.
+    const dist_fn fn = distance_points_kernel((flags & RT_DIST_EXHAUSTIVE) != 0u || s->ndist_blk <= kDistSmallBlocks);
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const dim3 grid((n + kWG - 1) / kWG), wg(kWG);
+    if (!(flags & RT_DIST_SORT))
+    {
+        hipLaunchKernelGGL(fn, grid, wg, 0, st, D);
+        RT_HIP(hipGetLastError());
+        return RT_OK;
+    }
+    // RT_DIST_SORT: the same kernel reading its points through the sorted words (as rays_sorted_order)
+    std::lock_guard<std::mutex> lk(s->mtx);
+    unsigned long long *keys = nullptr, *sorted = nullptr;
+    if (int rc = sorted_begin(s, st, n, &keys)) return rc;
+    hipLaunchKernelGGL(point_keys_kernel(), grid, wg, 0, st, D, keys);
+    RT_HIP(hipGetLastError());
+    if (int rc = sorted_finish(s, st, n, 32u, &sorted)) return rc;
+    D.order = sorted;
+    hipLaunchKernelGGL(fn, grid, wg, 0, st, D);
+    RT_HIP(hipGetLastError());
+    return rays_sorted_done(s, st);
+}
+
+int rt_primary_rays_device(rt_scene *s, const rt_frame *f, rt_ray *d_rays, void *hip_stream)
+{
+    if (!s || !d_rays) return fail(RT_E_INVALID, "NULL argument");
+    if (uintptr_t(d_rays) & 7u) return fail(RT_E_INVALID, "d_rays must be 8-byte aligned");
+    int rc = validate_frame(f);
+    if (rc) return rc;
+    const uint32_t spp = std::max(1u, f->spp);
+    const uint64_t n64 = uint64_t(f->width) * f->height * spp;
+    if (n64 >= 0x80000000ull) return fail(RT_E_INVALID, "more than 2^31 - 1 rays");
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if ((rc = ensure_device(s))) return rc;
+    if ((rc = prepare_samples(s, f, spp))) return rc;
+    KParams P;
+    frame_params(s, f, P);
+    // a launch of the scene that reads its frame tables: after every launch that may still read the old
+    // ones, and itself the scene's last launch (as launch_render's plain arms)
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if ((rc = begin_table_launch(s, st))) return rc;
+    const uint32_t n = uint32_t(n64);
+    hipLaunchKernelGGL(primary_rays_kernel(), dim3((n + kWG - 1) / kWG), dim3(kWG), 0, st, P,
+                       reinterpret_cast<float2 *>(d_rays), n);
+    RT_HIP(hipGetLastError());
+    return mark_own(s, st);
+}
+
+// An AO frame in one launch of k_render_ao (rt_ao.hip; include/rt_tracer.h has the contract).  Every argument is
+// checked before the scene is touched.  The launch is rt_primary_rays_device's kind (begin_table_launch): one of
+// the scene that reads its frame tables and no per-origin records.  The directions and rotations are kernel arguments.
+int rt_render_ao_device(rt_scene *s, const rt_frame *f, const rt_ao_params *ao, uint32_t *d_bgra, uint8_t *d_counts,
+                        void *hip_stream)
+{
+    if (!s) return fail(RT_E_INVALID, "scene is NULL");
+    if (!f) return fail(RT_E_INVALID, "frame is NULL");
+    if (!ao) return fail(RT_E_INVALID, "ao is NULL");
+    if (!d_bgra) return fail(RT_E_INVALID, "d_bgra is NULL");
+    int rc = validate_frame(f);
+    if (rc) return rc;
+    if (ao->num_dirs == 0 || ao->num_dirs > rtk::kAoMaxDirs) return fail(RT_E_INVALID, "num_dirs must be in [1, 64]");
+    if (std::isnan(ao->tmin) || std::isnan(ao->tmax)) return fail(RT_E_INVALID, "tmin / tmax is NaN");
+    if (!(ao->tmin < ao->tmax)) return fail(RT_E_INVALID, "tmin must be below tmax");
+    if (ao->flags & ~uint32_t(RT_AO_ROTATE)) return fail(RT_E_INVALID, "unknown rt_ao_flags bit");
+    const uint32_t spp = std::max(1u, f->spp);
+    if (!(is_pow2(spp) && spp <= 64)) return fail(RT_E_INVALID, "rt_render_ao_device needs spp to be a power of two <= 64");
+    if (f->intersector != RT_ISECT_GRID || f->tri_test != RT_TRI_MOLLER_TRUMBORE)
+        return fail(RT_E_INVALID, "rt_render_ao_device needs RT_ISECT_GRID and RT_TRI_MOLLER_TRUMBORE");
+    const uint64_t n64 = uint64_t(f->width) * f->height * spp;
+    if (n64 >= 0x80000000ull) return fail(RT_E_INVALID, "more than 2^31 - 1 samples");
+    rtk::KAo G;
+    std::memset(&G.a, 0, sizeof(G.a));
+    G.a.num_dirs = ao->num_dirs;
+    G.a.flags = ao->flags;
+    G.a.tmin = ao->tmin;
+    G.a.tmax = ao->tmax;
+    G.a.counts = d_counts;
+    if (ao->dirs)
+    {
+        for (uint32_t i = 0; i < 3u * ao->num_dirs; i++)
+        {
+            if (!std::isfinite(ao->dirs[i])) return fail(RT_E_INVALID, "dirs holds a non-finite entry");
+            G.a.dirs[i] = ao->dirs[i];
+        }
+    }
+    else if ((rc = rt_ao_table(ao->num_dirs, G.a.dirs)))
+        return rc;
+    if ((rc = rt_ao_rotations(G.a.rot))) return rc;
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if ((rc = ensure_device(s))) return rc;
+    if ((rc = prepare_samples(s, f, spp))) return rc;
+    KParams& P = G.p;
+    query_params(s, P, f);
+    const uint32_t tiles = region_params(P, 0, 0, f->width, f->height, d_bgra, f->width, 0u);
+    const uint32_t wgpt = (kTilePix * spp) / kWG;       // = spp: one wave per 64 sample slots of a tile
+    const uint64_t blocks = uint64_t(tiles) * wgpt;
+    if (blocks > 0x3FFFFFFFull) return fail(RT_E_INVALID, "frame too large for one launch");
+    launch_shape(P, wgpt, uint32_t(blocks));            // (k_render_ao reads the tile half alone)
+    const int var = kVarRays | kVarWaveGate | kVarDistSkip | scene_traversal_bits(s);
+    const rtk::ao_fn fn = rtk::render_ao_kernel(var);
+    if (!fn) return fail(RT_E_INVALID, "kernel variant not built: " + std::to_string(var));
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if ((rc = begin_table_launch(s, st))) return rc;
+    // the dispatch carries the scene's completion event, an event nothing still holds (launch_render's plain arm):
+    // the predecessor's event, which order_all kept as ev_prev, stays what it was, so a capture of this call after
+    // ONE warm-up queries no event recorded on the capturing stream
+    hipEvent_t stop = nullptr;
+    if ((rc = mark_free(s, nullptr, &stop))) return rc;
+    hipExtLaunchKernelGGL(fn, dim3(uint32_t(blocks)), dim3(kWG), 0, st, nullptr, stop, 0u, G);
+    RT_HIP(hipGetLastError());
+    return RT_OK;
+}
+
+} // extern "C"

@@ -23,14 +23,14 @@ __device__ __forceinline__ bool finite_f32(float x)
 // rt_frame.cam's 3x3 makes it (the direction is normalised before the matrix, rtd::dir_from_xy): an
 // orthonormal camera's are far inside, and for any other the host bounds |d|_inf per frame from the matrix
 // (rt_cam_bound.h) and launches the instantiation without kVarFastRcp when the bound exceeds kRcpMaxDir
-// (rt_tracer.hip, frame_traversal_bits).
+// (rt_launch.hip, frame_traversal_bits).
 constexpr float kRcpMaxDir = 8.0f;
 static_assert(double(kRcpMaxDir) == kCamRcpMaxDir, "rt_cam_bound.h bounds camera directions against kRcpMaxDir");
 
 // RT_RAYS_SORT: a ray's sort word is index << kKeyBits | key (rt_rays.hip, k_ray_keys)
 constexpr uint32_t kKeyBits = 32;
 
-// the ray kernels' variants: kRaysBase [| kVarFastRcp] [| kRaysBox] (rt_tracer.hip scene_traversal_bits)
+// the ray kernels' variants: kRaysBase [| kVarFastRcp] [| kRaysBox] (rt_launch.hip scene_traversal_bits)
 constexpr int kRaysBase = kVarRays | kVarWaveGate | kVarDistSkip;
 constexpr int kRaysBox = kVarPackedRem | kVarSkipRun;
 

@@ -12,7 +12,7 @@
 // D with |D_i| <= Dmax = 1.0001.  GenerateRay normalises the camera-space direction and multiplies by the
 // camera's 3x3 AFTERWARDS, so this holds for an orthonormal camera and not for any rt_frame.cam: the host
 // bounds |D_i| per frame from the matrix (rt_cam_bound.h) and passes the gate records only to frames inside
-// Dmax (rt_tracer.hip, frame_gated); the others take the ungated loop.  u = 2^-24, fl() = one f32 rounding,
+// Dmax (rt_launch.hip, frame_gated); the others take the ungated loop.  u = 2^-24, fl() = one f32 rounding,
 // g_k = k u / (1 - k u).  The reference computes (rtd::mt_rec_first, the order of triangle.h:45-87)
 //     p     = fl(D x e2)                          each component fl(fl(a b) - fl(c d))
 //     det_r = fl(fl(fl(e1x px) + fl(e1y py)) + fl(e1z pz)),   y_r likewise with T for e1

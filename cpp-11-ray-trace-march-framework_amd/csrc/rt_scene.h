@@ -1,5 +1,5 @@
 // rt_scene.h -- the library's scene object (struct rt_scene, opaque in the C ABI) and the host
-// functions rt_tracer.hip and rt_plan.hip share.  Not part of the ABI.
+// functions the host files (rt_tracer.hip, rt_launch.hip, rt_queries.hip) and rt_plan.hip share.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 

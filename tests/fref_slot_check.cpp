@@ -9,7 +9,7 @@
 // library grants only to a launch of one distinct origin that fref_overlap_ok accepts (launch_batch,
 // launch_render; an overlap refused for any other reason is an ordered launch).
 //
-// launch() below drives the header exactly as rt_tracer.hip does (order_all -> fref_ordered;
+// launch() below drives the header exactly as rt_launch.hip does (order_all -> fref_ordered;
 // ensure_origin_terms -> fref_slot_for_launch + fref_computed; fref_launched).  Everything it is checked
 // against is kept here, without the header's masks: what each buffer truly holds, which launches may still
 // run and what they read.
@@ -85,7 +85,7 @@ bool launch(State& s, const Kind& k, uint64_t *v, Tally& tl)
 {
     const uint32_t (*ob)[3] = k.ob;
     const int distinct = k.distinct;
-    // ---- the library's side: the header's functions, called as rt_tracer.hip calls them
+    // ---- the library's side: the header's functions, called as rt_launch.hip calls them
     bool overlap = k.ask && distinct == 1 && s.t.any;
     for (int i = 0; i < k.n && overlap; i++) overlap = rtk::fref_overlap_ok(s.f, ob[i]);
     if (!overlap) rtk::fref_ordered(s.f);

@@ -3,7 +3,7 @@
 tests/test_gpu_ray_variants.py and tests/test_gpu_variants.py (CallerBuilt).  A plain module, not a conftest.
 
 rt_trace_rays_device, rt_occluded_rays_device and rt_render_ao_device each ship four instantiations, picked by
-scene_traversal_bits() (rt_tracer.hip) from rt_scene_info.  The scenes of tests/ray_sets.py all have
+scene_traversal_bits() (rt_launch.hip) from rt_scene_info.  The scenes of tests/ray_sets.py all have
 rcp_safe = pack_ok = 1 and box words (stack2100: no cell words at all).  These seven do not:
 
   name              mesh, grid                                          rt_scene_info               kernel variant

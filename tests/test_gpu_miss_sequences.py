@@ -1,4 +1,4 @@
-"""The miss skip's host logic across SEQUENCES of frames (ensure_miss_mask / miss_launched, csrc/rt_tracer.hip;
+"""The miss skip's host logic across SEQUENCES of frames (ensure_miss_mask / miss_launched, csrc/rt_launch.hip;
 DESIGN.md §4.32; harness: tests/miss_skip_cases.py).
 
 A mask is keyed by the camera, the frame's shape and the version of the camera-space tables (tab_epoch: the field of

@@ -7,6 +7,7 @@ change a packed byte -- tests/test_gamma_exhaustive.py).
 """
 import hashlib
 import os
+import re
 
 import numpy as np
 import pytest
@@ -697,6 +698,41 @@ def test_wave_clock_debug_arm(scenes):
     assert clk[:, 2].any() or clk[:, 3].any()
 
 
+def _batch_pair(scenes, kernel=0):
+    """Scenes 1 and 8 at 160x120x4 as one rt_render_batch_device call: (scenes, frames, outputs, render)."""
+    import torch
+    gss = [scenes(1)[1], scenes(8)[1]]
+    fs = [g.frame(160, 120, 4, kernel=kernel) for g in gss]
+    outs = [torch.zeros(160 * 120, dtype=torch.int32, device="cuda") for _ in gss]
+
+    def render():
+        rtm.render_batch_device(gss, fs, [o.data_ptr() for o in outs], stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        return [o.cpu().numpy().view(np.uint32).reshape(120, 160) for o in outs]
+    return gss, fs, outs, render
+
+
+def test_wave_clock_batched(scenes):
+    """RT_KERNEL_FLAG_WAVE_CLOCK on every frame of a batch: still one launch, the frames untouched, and scene 0
+    holds the batch's records -- one per lane item of both frames, then kWhMax x 17 of the wide section."""
+    with open(os.path.join(os.path.dirname(rtm.__file__), "csrc", "rt_kparams.h")) as fh:
+        wh_max = int(re.search(r"constexpr uint32_t kWhMax = (\d+);", fh.read()).group(1))
+    gss, _, _, plain = _batch_pair(scenes)
+    want = plain()
+    _, _, _, clocked = _batch_pair(scenes, rtm.RT_KERNEL_AUTO | rtm.RT_KERNEL_FLAG_WAVE_CLOCK)
+    before = gss[0].info()
+    got = clocked()
+    after = gss[0].info()
+    assert after["batch_launches"] == before["batch_launches"] + 1
+    assert after["batch_fallbacks"] == before["batch_fallbacks"]
+    for g, w in zip(got, want):
+        np.testing.assert_array_equal(g, w)
+    lanes = 2 * 80 * 4 * 4                      # frames x tiles x workgroups per tile x waves
+    clk = gss[0].wave_clocks()
+    assert clk.shape == (lanes + wh_max * 17, 4)
+    assert (clk[:lanes, 1] >= clk[:lanes, 0]).all() and clk[:lanes, 0].any()
+
+
 def test_head_4096x4096x16(golden, scenes):
     """BASELINE config 4 (per-GPU work of the 8-GPU run is a subset of this frame)."""
     g = golden["frames_1080p4"]["head_4096x4096x16"]
@@ -809,6 +845,33 @@ def test_kernel_times_ring(scenes):
             assert len(gs.kernel_times()) == 0
     finally:
         gs.set_timing(8)
+
+
+def test_kernel_times_batched(scenes):
+    """A batched launch is timed once, on its first scene's ring: rt_scene_set_timing(1) on both scenes gives one
+    positive time per batch from scene 0 and none from the other; (0) none from either.  The frames are the
+    single-frame renders."""
+    gss, fs, _, render = _batch_pair(scenes)
+    want = [g.render_frame(f) for g, f in zip(gss, fs)]
+    try:
+        for g in gss:
+            g.set_timing(1)
+            g.kernel_times()
+        before = gss[0].info()["batch_launches"]
+        for _ in range(3):
+            for got, w in zip(render(), want):
+                np.testing.assert_array_equal(got, w)
+        assert gss[0].info()["batch_launches"] == before + 3
+        t = gss[0].kernel_times()
+        assert len(t) == 3 and (t > 0).all(), t
+        assert len(gss[1].kernel_times()) == 0
+        for g in gss:
+            g.set_timing(0)
+        render()
+        assert len(gss[0].kernel_times()) == 0 and len(gss[1].kernel_times()) == 0
+    finally:
+        for g in gss:
+            g.set_timing(8)
 
 
 def test_framebuffer_tile_pool_drop_in(golden, scenes, tmp_path):

@@ -1,7 +1,7 @@
 """The ray, occlusion and AO kernels on every scene-dependent instantiation, against the REFERENCE.
 
 rt_trace_rays_device, rt_occluded_rays_device and rt_render_ao_device each ship four instantiations
-(kRaysBase [| kVarFastRcp] [| kRaysBox], scene_traversal_bits in rt_tracer.hip).  The scenes of tests/test_gpu_ray_sets.py
+(kRaysBase [| kVarFastRcp] [| kRaysBox], scene_traversal_bits in rt_launch.hip).  The scenes of tests/test_gpu_ray_sets.py
 all run the first (stack2100: the third).  The seven scenes of tests/ray_variant_scenes.py reach the others, and what
 only they reach inside the walk:
 

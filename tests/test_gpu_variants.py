@@ -1,7 +1,7 @@
 """Every scene-dependent kernel choice, reached on purpose.
 
 rt_scene_create derives four properties from the scene and the launcher picks its kernels from them
-(render_device, rt_tracer.hip; lanes_kernel, rt_kernels.hip):
+(render_device, rt_launch.hip; lanes_kernel, rt_kernels.hip):
 
   property (rt_scene_info)            false when                                  what changes
   packed_cells                        a cell of >= 2,048 references, or           no cell words at all: the plain CSR walk
