@@ -27,7 +27,7 @@ KERNEL_SOURCES = ("csrc/rt_kernels.hip", "csrc/rt_walk.h", "csrc/rt_kparams.h", 
                   "csrc/rt_scene.h", "csrc/rt_tracer.hip", "csrc/rt_grid_build.hip", "csrc/rt_device.h",
                   "csrc/rt_internal.h", "csrc/rt_box_words.h", "csrc/rt_fref_slots.h", "csrc/rt_cam_bound.h", "csrc/rt_record_gate.h", "csrc/rt_setup_div.h", "csrc/rt_miss_mask.h", "csrc/rt_rays.hip",
                   "csrc/rt_ray_common.h", "csrc/rt_occlusion.hip", "csrc/rt_ao.hip", "csrc/rt_distance.hip",
-                  "csrc/rt_dist_tree.h", "csrc/rt_launch.hip", "csrc/rt_queries.hip", "csrc/rt_launch.h", "csrc/Makefile",
+                  "csrc/rt_dist_tree.h", "csrc/rt_march.hip", "csrc/rt_dist_sweep.h", "csrc/rt_launch.hip", "csrc/rt_queries.hip", "csrc/rt_launch.h", "csrc/Makefile",
                   "../include/rt_tracer.h")
 
 
@@ -59,6 +59,8 @@ RT_ISECT_RAY_MARCH = 2
 RT_RAYS_COUNT, RT_RAYS_SORT = 1, 2      # rt_trace_rays_device flags
 RT_AO_ROTATE = 1                        # rt_render_ao_device flags
 RT_DIST_EXHAUSTIVE, RT_DIST_SORT = 1, 2  # rt_distance_points_device flags
+RT_MARCH_EXHAUSTIVE, RT_MARCH_SORT = 1, 2  # rt_march_rays_device flags
+MARCH_MAX_STEPS = 4096                  # rt_march_params.max_steps' upper bound (kMarchMaxSteps)
 AO_MAX_DIRS = 64
 SHARD_TILE = 16
 
@@ -74,7 +76,7 @@ TRACER_SYMBOLS = [
     "rt_render_records_device", "rt_render_frame_host_tiled", "rt_fref_buffer_bytes",
     "rt_trace_rays_device", "rt_primary_rays_device", "rt_occluded_rays_device",
     "rt_ao_table", "rt_ao_rotations", "rt_render_ao_device", "rt_distance_points_device",
-    "rt_debug_miss_mask", "rt_debug_lane_launches",
+    "rt_march_rays_device", "rt_debug_miss_mask", "rt_debug_lane_launches",
 ]
 MAX_BATCH = 10                           # frames per rt_render_batch_device launch (kMaxBatch)
 
@@ -142,6 +144,14 @@ class PointDistRec(ctypes.Structure):       # rt_point_dist, 8 B
     _fields_ = [("dist", c_f32), ("tri", c_u32)]
 
 
+class MarchHitRec(ctypes.Structure):        # rt_march_hit, 16 B
+    _fields_ = [("t", c_f32), ("dist", c_f32), ("tri", c_u32), ("steps", c_u32)]
+
+
+class MarchParams(ctypes.Structure):        # rt_march_params
+    _fields_ = [("max_steps", c_u32), ("min_dist", c_f32)]
+
+
 class AoParams(ctypes.Structure):           # rt_ao_params
     _fields_ = [("num_dirs", c_u32), ("tmin", c_f32), ("tmax", c_f32), ("dirs", ctypes.POINTER(c_f32)),
                 ("flags", c_u32)]
@@ -175,6 +185,11 @@ POINT_DIST_DTYPE = np.dtype([("dist", "<f4"), ("tri", "<u4")])
 POINT_WORDS, POINT_DIST_WORDS = 3, 2
 # GpuScene.distance's result: per-point columns, the closest points (or None) and the raw rt_point_dist words
 PointDist = collections.namedtuple("PointDist", ["dist", "tri", "closest", "raw"])
+# rt_march_hit (rt_march_rays_device): a miss is t = dist = 0, tri 0xFFFFFFFF, steps 0
+MARCH_HIT_DTYPE = np.dtype([("t", "<f4"), ("dist", "<f4"), ("tri", "<u4"), ("steps", "<u4")])
+MARCH_HIT_WORDS = 4
+# GpuScene.march's result: per-ray columns (hit = steps != 0) and the raw rt_march_hit words
+MarchHit = collections.namedtuple("MarchHit", ["hit", "t", "dist", "tri", "steps", "raw"])
 
 _tracer = None
 _host = None
@@ -235,6 +250,8 @@ def tracer_lib():
             L.rt_render_ao_device.argtypes = [vp, ctypes.POINTER(Frame), ctypes.POINTER(AoParams), vp, vp, vp]
         if hasattr(L, "rt_distance_points_device"):  # absent in earlier builds (A/B runs)
             L.rt_distance_points_device.argtypes = [vp, vp, c_u32, c_u32, vp, vp, vp]
+        if hasattr(L, "rt_march_rays_device"):       # absent in earlier builds (A/B runs)
+            L.rt_march_rays_device.argtypes = [vp, vp, c_u32, ctypes.POINTER(MarchParams), c_u32, vp, vp]
         L.rt_unshard_device.argtypes = [c_u32, c_u32, c_u32, vp, vp, vp]
         L.rt_last_kernel_ms.argtypes = [vp, ctypes.POINTER(c_f32)]
         L.rt_trace_samples.argtypes = [vp, ctypes.POINTER(Frame), c_u32, c_u32, c_u32, c_u32, vp]
@@ -949,6 +966,65 @@ class GpuScene:
         u32 = getattr(torch, "uint32", None)
         tri = raw[:, 1].view(u32) if u32 is not None else raw[:, 1]
         return PointDist(raw[:, 0].view(torch.float32), tri, cl, raw)
+
+    def march(self, rays, max_steps=128, min_dist=1e-3, exhaustive=False, sort=False, stream=None):
+        """rt_march_rays_device: Renderer::RayMarch over DistanceBruteForce for caller-supplied rays [n, 6] (origin,
+        direction; the direction is used as passed, not normalised) -- at most max_steps (1..4096) sphere-trace steps
+        per ray inside one launch, a hit when a step's distance is below min_dist (include/rt_tracer.h has the loop).
+
+        rays: a contiguous float32 torch CUDA tensor on the scene's device -- read in place through data_ptr(),
+        asynchronously on `stream` as trace_rays does, results as torch tensors on that device -- or a C-contiguous
+        float32 numpy array, which is uploaded and the results downloaded (synchronous).  Anything else (another
+        dtype, shape, device, a strided view, a CPU tensor), max_steps outside 1..4096 or a NaN min_dist raises
+        ValueError before any launch.
+
+        Returns MarchHit: hit bool [n] (steps != 0), t f32 [n] (the march's t after the last step; 0 on a miss), dist
+        f32 [n] (the last distance; 0 on a miss), tri u32 [n] (the lowest mesh triangle at that distance, 0xFFFFFFFF on
+        a miss; int32 bits where torch has no uint32), steps u32 [n] (0 on a miss), raw = the [n, 4] rt_march_hit
+        words.  exhaustive=True (RT_MARCH_EXHAUSTIVE) evaluates every triangle at every step and stops no miss early;
+        sort=True (RT_MARCH_SORT) marches the rays in RT_RAYS_SORT's order.  Both give the same bytes, in input order."""
+        import torch
+        host = isinstance(rays, np.ndarray)
+        if host:
+            if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != RAY_WORDS or not rays.flags["C_CONTIGUOUS"]:
+                raise ValueError("rays: a C-contiguous float32 array of shape [n, 6]")
+        elif isinstance(rays, torch.Tensor):
+            if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != RAY_WORDS:
+                raise ValueError("rays: a float32 tensor of shape [n, 6]")
+            if not rays.is_cuda or rays.device.index != self.device:
+                raise ValueError(f"rays: a tensor on cuda:{self.device} (host memory is not read in place)")
+            if not rays.is_contiguous():
+                raise ValueError("rays: a contiguous tensor (a strided view would be read as other rays)")
+        else:
+            raise ValueError("rays: a torch CUDA tensor or a numpy array")
+        if isinstance(max_steps, bool) or not isinstance(max_steps, (int, np.integer)) or not 1 <= max_steps <= MARCH_MAX_STEPS:
+            raise ValueError(f"max_steps: an integer in [1, {MARCH_MAX_STEPS}]")
+        try:
+            min_dist = float(min_dist)
+        except (TypeError, ValueError):
+            raise ValueError("min_dist: a number") from None
+        if min_dist != min_dist:
+            raise ValueError("min_dist: not NaN")
+        d_rays = torch.from_numpy(rays).to(f"cuda:{self.device}") if host else rays
+        n = d_rays.shape[0]
+        dev = d_rays.device
+        raw = torch.empty((n, MARCH_HIT_WORDS), dtype=torch.int32, device=dev)
+        flags = (RT_MARCH_EXHAUSTIVE if exhaustive else 0) | (RT_MARCH_SORT if sort else 0)
+        if stream is not None and int(stream) != torch.cuda.current_stream(dev).cuda_stream:
+            raw.record_stream(torch.cuda.ExternalStream(int(stream), device=dev))      # (as trace_rays)
+        mp = MarchParams(int(max_steps), min_dist)
+        L = tracer_lib()
+        _check(L.rt_march_rays_device(self._h, ctypes.c_void_p(d_rays.data_ptr()), n, ctypes.byref(mp), flags,
+                                      ctypes.c_void_p(raw.data_ptr()),
+                                      ctypes.c_void_p(self._stream(torch, stream))), L, "rt_march_rays_device")
+        if host:
+            if stream is not None:
+                torch.cuda.synchronize(dev)            # the copy below runs on torch's stream
+            r = raw.cpu().numpy().view(MARCH_HIT_DTYPE).reshape(n)
+            return MarchHit(r["steps"] != 0, r["t"], r["dist"], r["tri"], r["steps"], r)
+        u32 = getattr(torch, "uint32", None)
+        tri, steps = (raw[:, 2].view(u32), raw[:, 3].view(u32)) if u32 is not None else (raw[:, 2], raw[:, 3])
+        return MarchHit(raw[:, 3] != 0, raw[:, 0].view(torch.float32), raw[:, 1].view(torch.float32), tri, steps, raw)
 
     def render_ao(self, frame, num_dirs=4, tmin=0.0, tmax=float("inf"), dirs=None, rotate=True, out=None,
                   counts=False, stream=None):

@@ -415,5 +415,21 @@ using dist_fn = void (*)(KDist);
 using point_keys_fn = void (*)(KDist, unsigned long long *);
 dist_fn distance_points_kernel(bool exhaustive);
 point_keys_fn point_keys_kernel();
+// rt_march.hip: k_march_rays<exhaustive>(KMarch) -- rt_march_rays_device: Renderer::RayMarch over the distance
+// queries' arrays for caller-supplied rays.  d holds the scene's distance arrays as rt_distance_points_device fills
+// them, d.n the ray count and d.order the sorted words (RT_MARCH_SORT: k_ray_keys' words; else null); d.points,
+// d.out and d.closest are unused.
+struct KMarch
+{
+    KDist d;
+    const float2 *rays;                 // [n] rt_ray, 3 float2 each
+    uint2 *out;                         // [n] rt_march_hit, 2 uint2 each (8-byte aligned)
+    uint32_t max_steps;                 // 1..kMarchMaxSteps
+    float min_dist;                     // not NaN
+    float vmax[3];                      // the vertex box's max (its min: d.vmin), for the receding-miss stop
+};
+constexpr uint32_t kMarchMaxSteps = 4096;
+using march_fn = void (*)(KMarch);
+march_fn march_rays_kernel(bool exhaustive);
 
 } // namespace rtk

@@ -1,6 +1,6 @@
 // rt_launch.h -- what the library's three host files share (not part of the ABI): rt_tracer.hip (ABI basics,
 // rt_scene_create / destroy, rt_debug_*), rt_launch.hip (events and ordering, frame tables, the render launches
-// and the copy-back paths) and rt_queries.hip (samples, rays, occlusion, distance, primary rays, AO).  DESIGN.md
+// and the copy-back paths) and rt_queries.hip (samples, rays, occlusion, distance, marches, primary rays, AO).  DESIGN.md
 // §4.34 says which of these a new entry point must call.
 #pragma once
 #include <string>

@@ -1,7 +1,8 @@
 // rt_queries.hip -- the query entry points of librt_tracer.so (include/rt_tracer.h): per-sample records of a frame
 // rectangle (rt_trace_samples), caller-supplied rays (rt_trace_rays_device), occlusion (rt_occluded_rays_device),
-// point distances (rt_distance_points_device), a frame's primary rays (rt_primary_rays_device) and AO frames
-// (rt_render_ao_device).  Kernels: rt_kernels.hip, rt_rays.hip, rt_occlusion.hip, rt_distance.hip, rt_ao.hip.
+// point distances (rt_distance_points_device), marches (rt_march_rays_device), a frame's primary rays
+// (rt_primary_rays_device) and AO frames (rt_render_ao_device).  Kernels: rt_kernels.hip, rt_rays.hip,
+// rt_occlusion.hip, rt_distance.hip, rt_march.hip, rt_ao.hip.
 // What they share with the render launches (rt_launch.hip) is declared in rt_launch.h.
 
 #include <hip/hip_runtime.h>
@@ -73,6 +74,32 @@ int rays_sorted_done(rt_scene *s, hipStream_t st)
     s->rays_stream = st;
     s->rays_ev_recorded = true;
     return RT_OK;
+}
+
+// The scene's distance arrays (rt_dist_tree.h) as rt_scene_create wrote them: what the distance and march kernels share
+void dist_params(const rt_scene *s, KDist& D)
+{
+    std::memset(&D, 0, sizeof(D));
+    D.tri_dist = s->d_tridist;
+    D.tri_idx = s->d_distidx;
+    D.blk = s->d_distblk;
+    D.blk_key = s->d_distkey;
+    D.nodes = s->d_distnodes;
+    D.ntris = s->ntris;
+    D.nblk = s->ndist_blk;
+    D.nlevels = s->dist_levels;
+    for (uint32_t l = 0; l < kDistLevels; l++)
+    {
+        D.lvl_off[l] = s->dist_lvl_off[l];
+        D.lvl_n[l] = s->dist_lvl_n[l];
+    }
+    D.scene_scale = s->scene_scale;
+    for (int a = 0; a < 3; a++)
+    {
+        const float ext = s->vmax[a] - s->vmin[a];
+        D.vmin[a] = s->vmin[a];
+        D.vinv[a] = ext > 0.0f && 1024.0f / ext <= rtd::kFltMax ? 1024.0f / ext : 0.0f;
+    }
 }
 } // namespace
 
@@ -215,27 +242,7 @@ int rt_distance_points_device(rt_scene *s, const float *d_points, uint32_t n, ui
     if (uintptr_t(d_out) & 7u) return fail(RT_E_INVALID, "d_out must be 8-byte aligned");
     if (int rc = ensure_device(s)) return rc;
     KDist D;
-    std::memset(&D, 0, sizeof(D));
-    D.tri_dist = s->d_tridist;
-    D.tri_idx = s->d_distidx;
-    D.blk = s->d_distblk;
-    D.blk_key = s->d_distkey;
-    D.nodes = s->d_distnodes;
-    D.ntris = s->ntris;
-    D.nblk = s->ndist_blk;
-    D.nlevels = s->dist_levels;
-    for (uint32_t l = 0; l < kDistLevels; l++)
-    {
-        D.lvl_off[l] = s->dist_lvl_off[l];
-        D.lvl_n[l] = s->dist_lvl_n[l];
-    }
-    D.scene_scale = s->scene_scale;
-    for (int a = 0; a < 3; a++)
-    {
-        const float ext = s->vmax[a] - s->vmin[a];
-        D.vmin[a] = s->vmin[a];
-        D.vinv[a] = ext > 0.0f && 1024.0f / ext <= rtd::kFltMax ? 1024.0f / ext : 0.0f;
-    }
+    dist_params(s, D);
     D.points = d_points;
     D.n = n;
     D.out = reinterpret_cast<uint2 *>(d_out);
@@ -261,6 +268,51 @@ int rt_distance_points_device(rt_scene *s, const float *d_points, uint32_t n, ui
     if (int rc = sorted_finish(s, st, n, 32u, &sorted)) return rc;
     D.order = sorted;
     hipLaunchKernelGGL(fn, grid, wg, 0, st, D);
+    RT_HIP(hipGetLastError());
+    return rays_sorted_done(s, st);
+}
+
+// Renderer::RayMarch for caller-supplied rays (include/rt_tracer.h; kernel: rt_march.hip).  The argument rules, the
+// sort path (RT_RAYS_SORT's own: k_ray_keys' words, the scene's sort scratch and its event) and the absence of state
+// without RT_MARCH_SORT are rt_trace_rays_device's.
+int rt_march_rays_device(rt_scene *s, const rt_ray *d_rays, uint32_t n, const rt_march_params *params, uint32_t flags,
+                         rt_march_hit *d_out, void *hip_stream)
+{
+    if (!s) return fail(RT_E_INVALID, "scene is NULL");
+    if (flags & ~uint32_t(RT_MARCH_EXHAUSTIVE | RT_MARCH_SORT)) return fail(RT_E_INVALID, "unknown rt_march_flags bit");
+    const rt_march_params mp = params ? *params : rt_march_params{ kMarchSteps, 0.001f };
+    if (mp.max_steps == 0 || mp.max_steps > kMarchMaxSteps) return fail(RT_E_INVALID, "max_steps must be in [1, 4096]");
+    if (std::isnan(mp.min_dist)) return fail(RT_E_INVALID, "min_dist is NaN");
+    if (n >= 0x80000000u) return fail(RT_E_INVALID, "n must be below 2^31");
+    if (n == 0) return RT_OK;
+    if (!d_rays) return fail(RT_E_INVALID, "d_rays is NULL");
+    if (!d_out) return fail(RT_E_INVALID, "d_out is NULL");
+    if ((uintptr_t(d_rays) | uintptr_t(d_out)) & 7u) return fail(RT_E_INVALID, "d_rays and d_out must be 8-byte aligned");
+    if (int rc = ensure_device(s)) return rc;
+    KMarch M;
+    dist_params(s, M.d);
+    M.d.n = n;
+    M.rays = reinterpret_cast<const float2 *>(d_rays);
+    M.out = reinterpret_cast<uint2 *>(d_out);
+    M.max_steps = mp.max_steps;
+    M.min_dist = mp.min_dist;
+    for (int a = 0; a < 3; a++) M.vmax[a] = s->vmax[a];
+    const march_fn fn = march_rays_kernel((flags & RT_MARCH_EXHAUSTIVE) != 0u);
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const dim3 grid((n + kWG - 1) / kWG), wg(kWG);
+    if (!(flags & RT_MARCH_SORT))
+    {
+        hipLaunchKernelGGL(fn, grid, wg, 0, st, M);
+        RT_HIP(hipGetLastError());
+        return RT_OK;
+    }
+    KParams P;
+    query_params(s, P);
+    std::lock_guard<std::mutex> lk(s->mtx);
+    unsigned long long *sorted = nullptr;
+    if (int rc = rays_sorted_order(s, P, M.rays, n, st, &sorted)) return rc;
+    M.d.order = sorted;
+    hipLaunchKernelGGL(fn, grid, wg, 0, st, M);
     RT_HIP(hipGetLastError());
     return rays_sorted_done(s, st);
 }

@@ -475,6 +475,50 @@ enum rt_dist_flags {
 int  rt_distance_points_device(rt_scene *scene, const float *d_points /* [n][3] */, uint32_t n, uint32_t flags,
                                rt_point_dist *d_out, float *d_closest /* [n][3] or NULL */, void *hip_stream);
 
+/* ---- march queries ---------------------------------------------------------------------
+ * Renderer::RayMarch (renderer.cpp:24-41) over DistanceBruteForce for rays the CALLER supplies: the sphere trace of
+ * RT_ISECT_RAY_MARCH as a query of its own, every step inside one launch. */
+typedef struct rt_march_hit { float t; float dist; uint32_t tri; uint32_t steps; } rt_march_hit;   /* 16 B */
+enum rt_march_flags {
+    RT_MARCH_EXHAUSTIVE = 1, /* every triangle at every step, no culling, no early stop: the A/B and parity arm */
+    RT_MARCH_SORT       = 2  /* march the rays in RT_RAYS_SORT's order (direction octant, entry cell): for rays in no
+                                useful order.  Same bytes, in input order.  The sort, its scratch and its rules are
+                                RT_RAYS_SORT's */
+};
+typedef struct rt_march_params { uint32_t max_steps; float min_dist; } rt_march_params;  /* NULL = {128, 0.001f} */
+/* Ray (o, d) = d_rays[i] gives, in d_out[i] (input order; exactly n records are written), what this loop leaves.
+ * Every float operation is ONE f32 rounding and there is no FMA:
+ *     t = 0;
+ *     for (s = 0; s < max_steps; s++) {
+ *         pos  = o + t * d;                 per component: the product rounded, then the sum
+ *         dist = DistanceBruteForce(pos);   rt_distance_points_device's dist for pos, bit for bit
+ *         t   += dist;
+ *         if (dist < min_dist) -> HIT at step s + 1
+ *     }
+ *     -> MISS
+ *   HIT   t = the value after the add (what RayMarch returns), dist = the last distance, tri = the lowest mesh
+ *         triangle index whose distance to the last pos equals dist (rt_distance_points_device's rule; 0xFFFFFFFF if
+ *         none attains it), steps = s + 1 >= 1.
+ *   MISS  t = 0, dist = 0, tri = 0xFFFFFFFF, steps = 0: steps == 0 is the miss test.  (The reference's t after a failed
+ *         march means nothing; fixing these values is what lets a proven miss stop early.)
+ * d is used as passed, not normalised; the march is a sound sphere trace (it cannot step through a surface) only for
+ * |d| <= 1.  No ray is special-cased: the loop is defined for NaN, +-inf, denormal, huge and zero components (dist
+ * is never NaN, t may reach inf) and the result is the loop's.  With the defaults {128, 0.001f} and a frame's
+ * rt_primary_rays_device rays, hit, t and steps are RT_ISECT_RAY_MARCH's (rt_trace_samples), a miss apart, which
+ * reports t and 128 steps there.
+ * The default arm evaluates each step as rt_distance_points_device does (the box hierarchy; every triangle on a mesh
+ * of at most 64 triangles) and ends a ray as a MISS once it provably recedes from the vertex box for good (DESIGN.md
+ * §4.35 has the condition and its proof); RT_MARCH_EXHAUSTIVE does neither.  Both give the same bytes.
+ *   n == 0: RT_OK, nothing written.  n < 2^31.  max_steps in 1..4096 (one launch stays bounded).  min_dist: NaN is
+ *   RT_E_INVALID, every other value means what the loop makes of it (0 and negatives never hit, +inf hits at step 1).
+ *   A NULL scene, d_rays or d_out, a d_rays or d_out that is not 8-byte aligned, or an unknown flag: RT_E_INVALID
+ *   before any launch, nothing written.
+ * Asynchronous on hip_stream.  Without RT_MARCH_SORT the call is stateless: no lock, no event, no allocation, only
+ * arrays rt_scene_create wrote are read, it needs no ordering against the scene's render launches and can be captured
+ * in a graph.  With RT_MARCH_SORT it shares the state of RT_RAYS_SORT and follows its rules. */
+int  rt_march_rays_device(rt_scene *scene, const rt_ray *d_rays, uint32_t n, const rt_march_params *params,
+                          uint32_t flags, rt_march_hit *d_out, void *hip_stream);
+
 /* Render-kernel time of the last timed rendering call on this scene (ms): the HIP events on the
  * launch stream immediately around its render kernel(s), as rt_kernel_times.  Waits for them. */
 int  rt_last_kernel_ms(rt_scene *scene, float *ms);

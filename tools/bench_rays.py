@@ -28,10 +28,17 @@ on the same frame, in the same session, into profiles/ao_bench.json (ao_legs).
 default arm against RT_DIST_EXHAUSTIVE and a chunked torch brute force, into profiles/distance_bench.json
 (distance_legs).
 
+--march measures rt_march_rays_device (GpuScene.march) on the 1920x1080x1 camera rays: the fused call against the
+loop of GpuScene.distance calls it replaces, RT_MARCH_EXHAUSTIVE, the other seed and the arm without the early stop
+(--ab-lib builds of tools/build_variant.sh) and the RT_ISECT_RAY_MARCH frame, into profiles/march_bench.json
+(march_legs).
+
     python3 tools/bench_rays.py --parent-lib librt_tracer_parent.so [--ab-lib other=librt_tracer_other.so]
     python3 tools/bench_rays.py --occlusion
     python3 tools/bench_rays.py --ao
     python3 tools/bench_rays.py --distance
+    tools/build_variant.sh seedmorton -DRT_MARCH_SEED=0 && tools/build_variant.sh nostop -DRT_MARCH_STOP=0 &&
+        python3 tools/bench_rays.py --march --ab-lib seed_morton=librt_tracer_seedmorton.so --ab-lib no_stop=librt_tracer_nostop.so
 """
 import argparse
 import importlib.util
@@ -422,6 +429,131 @@ def distance_legs(args):
     print("wrote", args.out)
 
 
+def march_loop(gs, rays, max_steps, min_dist, st, sort=False):
+    """What a caller had before rt_march_rays_device: the contract's loop as GpuScene.distance calls with torch float32
+    arithmetic between them (one torch operation per rounding: the same bytes), on the rays still marching, until
+    every ray is done -> the [n, 4] rt_march_hit words."""
+    n = rays.shape[0]
+    o, d = rays[:, :3].contiguous(), rays[:, 3:].contiguous()
+    t = torch.zeros(n, dtype=torch.float32, device=rays.device)
+    out = torch.zeros((n, 4), dtype=torch.int32, device=rays.device)
+    out[:, 2] = -1
+    idx = torch.arange(n, device=rays.device)
+    for s in range(max_steps):
+        if idx.numel() == 0:            # (a host read per step: the caller has to know when to stop)
+            break
+        prod = t[idx, None] * d[idx]
+        res = gs.distance((o[idx] + prod).contiguous(), sort=sort, stream=st)
+        tn = t[idx] + res.dist
+        t[idx] = tn
+        h = res.dist < min_dist
+        done = idx[h]
+        out[done, 0] = tn[h].view(torch.int32)
+        out[done, 1] = res.dist[h].view(torch.int32)
+        out[done, 2] = res.raw[h, 1]
+        out[done, 3] = s + 1
+        idx = idx[~h]
+    return out
+
+
+def idle_share(steps, max_steps, count_miss):
+    """Share of lane-steps idle in waves of 64 consecutive rays: 1 - sum(lane steps) / (64 x sum(the wave's longest
+    lane)), a hit marching its steps and a miss count_miss steps (max_steps: the arm without the early stop, exact;
+    1: a lower bound of what a stopped miss marches -- where a miss stopped cannot be read from the output)."""
+    s = np.where(steps == 0, count_miss, steps).astype(np.int64)
+    lanes = np.concatenate([s, np.zeros((-s.size) % 64, np.int64)]).reshape(-1, 64)
+    return round(1.0 - float(s.sum()) / float(lanes.max(1).sum() * 64), 4)
+
+
+def march_legs(args):
+    """--march: rt_march_rays_device (GpuScene.march), max_steps 128, min_dist 1e-3, into profiles/march_bench.json.
+    Rays: the 1920x1080x1 camera rays in camera order, shuffled (PCG64(41)), and shuffled with RT_MARCH_SORT.  Arms,
+    samples interleaved (measure), one launch per sample:
+      fused          the call as it ships;
+      distance_loop  march_loop: what a caller had before, the same bytes;
+      exhaustive     RT_MARCH_EXHAUSTIVE over the leg's first EXH_RAYS rays (compared per ray);
+      <--ab-lib>     the same call from variant builds: the other seed, no early stop.
+    Per scene also the RT_ISECT_RAY_MARCH frame of the same camera at spp 1 (render_frame_device between events: the
+    flat sweep of all block boxes per step against the hierarchy), and the idle share of lane-steps from `steps`."""
+    EXH_RAYS = 1 << 15
+    MAX_STEPS, MIN_DIST = 128, 1e-3
+    mods = {"this": load("rtm_this", None)}
+    for spec in args.ab_lib:
+        name, lib = spec.split("=", 1)
+        mods[name] = load("rtm_" + name, lib)
+    rtm = mods["this"]
+    res = {"tool": "tools/bench_rays.py --march", "frame": [W, H, 1], "max_steps": MAX_STEPS, "min_dist": MIN_DIST,
+           "launches_per_sample": args.steps, "warmup": args.warmup, "samples": 5, "build_hash": rtm.library_build_hash(),
+           "device": torch.cuda.get_device_name(0), "arms": {k: m.library_build_hash() for k, m in mods.items()},
+           "exhaustive_arm": f"RT_MARCH_EXHAUSTIVE over the first {EXH_RAYS} rays of a leg; rays/s compared",
+           "scenes": {}}
+    st = torch.cuda.current_stream().cuda_stream
+    for sid in args.scenes:
+        hs = {k: m.HostScene.load(sid) for k, m in mods.items()}
+        gs = {k: m.GpuScene(hs[k], 0) for k, m in mods.items()}
+        g0 = gs["this"]
+        rays = g0.primary_rays(g0.frame(W, H, 1))
+        torch.cuda.synchronize()
+        n = rays.shape[0]
+        entry = {"triangles": int(hs["this"].mesh()[1].shape[0]), "rays": int(n)}
+
+        def leg(r, sort=False):
+            ref = g0.march(r, MAX_STEPS, MIN_DIST, sort=sort).raw
+            sub = r[:EXH_RAYS].contiguous()
+            same = {"distance_loop": bool(torch.equal(march_loop(g0, r, MAX_STEPS, MIN_DIST, st, sort), ref)),
+                    "exhaustive": bool(torch.equal(g0.march(sub, MAX_STEPS, MIN_DIST, exhaustive=True, sort=sort).raw, ref[:EXH_RAYS]))}
+            fns = {"fused": lambda: g0.march(r, MAX_STEPS, MIN_DIST, sort=sort, stream=st),
+                   "distance_loop": lambda: march_loop(g0, r, MAX_STEPS, MIN_DIST, st, sort),
+                   "exhaustive": lambda: g0.march(sub, MAX_STEPS, MIN_DIST, exhaustive=True, sort=sort, stream=st)}
+            for k, g in gs.items():
+                if k != "this":
+                    fns[k] = lambda g=g: g.march(r, MAX_STEPS, MIN_DIST, sort=sort, stream=st)
+                    same[k] = bool(torch.equal(g.march(r, MAX_STEPS, MIN_DIST, sort=sort).raw, ref))
+            out = measure(fns, n, args.steps, args.warmup, per_arm={"distance_loop": (1, 1, n), "exhaustive": (1, 1, sub.shape[0])})
+            for k in out:
+                out[k]["unit"] = "rays/s"
+                if k in same:
+                    out[k]["same_bytes_as_fused"] = same[k]
+            steps = ref[:, 3].cpu().numpy()
+            f, lp, ex = out["fused"], out["distance_loop"], out["exhaustive"]
+            o = {"rays": int(n), "sort": sort, "hits": int((steps != 0).sum()), "max_hit_steps": int(steps.max()), **out,
+                 "speedup_over_distance_loop": round(lp["ms"] / f["ms"], 3),
+                 "speedup_over_exhaustive_per_ray": round(f["per_s"] / ex["per_s"], 1),
+                 "beats_distance_loop": bool(f["ms"] < lp["ms"] * (1.0 - max(f["spread"], lp["spread"]))),
+                 "beats_exhaustive": bool(f["per_s"] * (1.0 - max(f["spread"], ex["spread"])) > ex["per_s"])}
+            for k in out:
+                if k not in ("fused", "distance_loop", "exhaustive"):
+                    o[f"fused_beats_{k}"] = bool(f["ms"] < out[k]["ms"] * (1.0 - max(f["spread"], out[k]["spread"])))
+                    o[f"{k}_over_fused"] = round(out[k]["ms"] / f["ms"], 3)
+            if not sort:
+                o["idle_lane_steps"] = {"misses_at_max_steps": idle_share(steps, MAX_STEPS, MAX_STEPS),
+                                        "misses_at_one_step": idle_share(steps, MAX_STEPS, 1)}
+            return o
+
+        entry["camera_order"] = leg(rays)
+        perm = torch.from_numpy(np.random.Generator(np.random.PCG64(41)).permutation(n)).cuda()
+        shuffled = rays[perm].contiguous()
+        entry["shuffled"] = leg(shuffled)
+        entry["shuffled_sorted"] = leg(shuffled, sort=True)
+        fm = g0.frame(W, H, 1, intersector=rtm.RT_ISECT_RAY_MARCH)
+        out = torch.empty(W * H, dtype=torch.int32, device="cuda")
+        fr = measure({"march_frame": lambda: g0.render_frame_device(fm, out.data_ptr(), st)}, n, args.steps, args.warmup)
+        fr["march_frame"]["unit"] = "samples/s"
+        entry["frame_ray_march_spp1"] = fr["march_frame"]
+        entry["frame_over_fused_camera_order"] = round(fr["march_frame"]["ms"] / entry["camera_order"]["fused"]["ms"], 3)
+        res["scenes"][str(sid)] = entry
+        print(json.dumps({str(sid): entry}), flush=True)
+        for g in gs.values():
+            g.close()
+        for h in hs.values():
+            h.close()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print("wrote", args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", type=int, nargs="+", default=[8, 1])
@@ -432,14 +564,21 @@ def main():
     ap.add_argument("--occlusion", action="store_true", help="the occlusion legs (occlusion_legs) instead of the ray legs")
     ap.add_argument("--ao", action="store_true", help="the AO-frame legs (ao_legs) instead of the ray legs")
     ap.add_argument("--distance", action="store_true", help="the distance-query legs (distance_legs) instead of the ray legs")
+    ap.add_argument("--march", action="store_true", help="the march-query legs (march_legs) instead of the ray legs; "
+                                                        "--steps / --warmup default to 1 there: a launch is long")
     ap.add_argument("--out", default=None, help="default: profiles/rays_bench.json (--occlusion: profiles/occlusion_bench.json; "
-                                                "--ao: profiles/ao_bench.json; --distance: profiles/distance_bench.json)")
+                                                "--ao: profiles/ao_bench.json; --distance: profiles/distance_bench.json; --march: profiles/march_bench.json)")
     args = ap.parse_args()
+    if args.march:
+        args.steps = 1 if args.steps == ap.get_default("steps") else args.steps
+        args.warmup = 1 if args.warmup == ap.get_default("warmup") else args.warmup
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "ao_bench.json" if args.ao else "distance_bench.json" if args.distance else
+        args.out = os.path.join(ROOT, "profiles", "march_bench.json" if args.march else "ao_bench.json" if args.ao else "distance_bench.json" if args.distance else
                                 "occlusion_bench.json" if args.occlusion else "rays_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_rays.py measures on the GPU; none is visible")
+    if args.march:
+        return march_legs(args)
     if args.distance:
         return distance_legs(args)
     if args.ao:

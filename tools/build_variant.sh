@@ -10,7 +10,7 @@ NAME=$1; shift
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize"
 TMP=$(mktemp -d)
 pids=()
-for tu in rt_kernels rt_plan rt_tracer rt_grid_build rt_rays rt_occlusion rt_ao; do
+for tu in rt_kernels rt_plan rt_tracer rt_grid_build rt_rays rt_occlusion rt_ao rt_distance rt_march rt_launch rt_queries; do
     /opt/rocm/bin/hipcc $FLAGS "$@" -DRT_SRC_HASH="\"variant-$NAME\"" -c -o "$TMP/$tu.o" "$C/$tu.hip" &
     pids+=($!)
 done
