@@ -1283,8 +1283,11 @@ __device__ __forceinline__ bool ray_march(const KParams& P, float ox, float oy, 
                 }
             }
             {
+                // the seed enters as any other member does: (d < dist) never selects a NaN (a triangle with
+                // coinciding vertices), which as a plain assignment would keep every later d < dist false
                 const float4 *r = P.tri_dist + 6 * size_t(best_k);
-                dist = rtd::dist_point_tri(px, py, pz, r[0], r[1], r[2], r[3], r[4], r[5]);
+                const float d = rtd::dist_point_tri(px, py, pz, r[0], r[1], r[2], r[3], r[4], r[5]);
+                dist = (d < dist) ? d : dist;
             }
             uint32_t evals = 1;
             const uint32_t start = __builtin_amdgcn_readfirstlane(best_k / kDistBlock);

@@ -868,6 +868,16 @@ void orc_kat_shade(const float *in, uint32_t n, float *out)
     }
 }
 
+// Another view for every later call on this scene (orc_render, orc_trace_samples: any tri_test / intersector):
+// Scene::GetCameraParameters' matrix and fov replaced in place.  The mesh and the grid do not depend on them.
+int orc_scene_set_view(orc_scene *h, const float *cam16, float fov)
+{
+    if (!h || !cam16) return 1;
+    std::memcpy(&h->s.cam[0][0], cam16, 64);
+    h->s.fov = fov;
+    return 0;
+}
+
 // orc_render with another camera (Scene::GetCameraParameters' matrix and fov replaced): the same
 // restated tile pool over a copy of the scene (test infrastructure: custom-view parity of the
 // product walk -- cameras inside the grid, axis-aligned views)

@@ -63,6 +63,8 @@ int orc_render(const orc_scene *s, uint32_t W, uint32_t H, uint32_t spp, uint32_
  * Scene::GetCameraParameters returns it, fov in degrees. */
 int orc_render_cam(const orc_scene *s, uint32_t W, uint32_t H, uint32_t spp, const float *cam16, float fov,
                    uint32_t *out_bgra, uint32_t *hit_ids);
+/* Replaces the scene's view for every later call (orc_render, orc_trace_samples, any tri_test / intersector). */
+int orc_scene_set_view(orc_scene *s, const float *cam16, float fov);
 /* orc_render_cam with the caller's sample offsets smp[2 spp] (rt_frame.sample_offsets) in place of the
    Hammersley table; smp NULL: the Hammersley table. */
 int orc_render_smp(const orc_scene *s, uint32_t W, uint32_t H, uint32_t spp, const float *cam16, float fov,

@@ -26,7 +26,7 @@
 //                                            --bmp: the reference's WriteBitmap of the gathered frame
 //   samples <scene.rtscene> W H spp x0 y0 w h <out.bin>    per-sample records; refdriver_instr
 //                                            (grid.cpp + ref_instr.h) appends voxel, steps, tests
-//   alt-samples <scene.rtscene> W H spp x0 y0 w h brute|march <out.bin>
+//   alt-samples <scene.rtscene> W H spp x0 y0 w h brute|march <out.bin> [--view <file>]
 //                                            records of Renderer::IntersectBruteForce / RayMarch
 //   render ... [--isect grid|brute|march]   the frame with another intersector (renderer.cpp:103-105)
 //   rays <scene.rtscene> <rays.f32> <out.rec> [res]   Grid::Intersect on caller-supplied rays: in n x 6 f32
@@ -862,7 +862,7 @@ int main(int argc, char **argv)
     }
 
     if ((cmd == "grid" && (argc == 4 || argc == 5)) || (cmd == "render" && argc >= 6) ||
-        (cmd == "samples" && argc >= 11) || (cmd == "alt-samples" && argc == 12) || (cmd == "rays" && (argc == 5 || argc == 6)))
+        (cmd == "samples" && argc >= 11) || (cmd == "alt-samples" && argc >= 12) || (cmd == "rays" && (argc == 5 || argc == 6)))
     {
         SceneFile sf;
         if (!ReadScene(argv[2], sf)) { std::fprintf(stderr, "bad scene file\n"); return 1; }

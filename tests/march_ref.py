@@ -96,6 +96,26 @@ def stop_condition(o, d, pos, vmin, vmax, scale, min_dist):
                 (thr >= FLT_MIN))
 
 
+def frame_stop_condition(d, pos, vmin, vmax, scale):
+    """The receding-miss stop of the FRAME march (ray_march's culled arm, csrc/rt_walk.h) at a step's position, its
+    float operations in their order -> bool [n].  Unlike the query's (stop_condition) it has neither the |dir|_1 factor
+    nor the E term: min_dist is 0.001, the rate threshold 2e-5 db whatever the direction's length.
+
+        margin = 1e-5 (|p|_inf + scene_scale)
+        w      = p - clamp(p, smin, smax)
+        db     = sqrtf(wx wx + wy wy + wz wz)       every product and sum one rounding, summed left to right
+        rate   = dx wx + dy wy + dz wz
+        fire iff db > 1.00001 (margin + 0.001) && rate >= 2e-5 db"""
+    d, pos = (np.ascontiguousarray(x, f32) for x in (d, pos))
+    with np.errstate(all="ignore"):
+        pmax = np.fmax(np.fmax(np.abs(pos[:, 0]), np.abs(pos[:, 1])), np.abs(pos[:, 2]))
+        margin = f32(1e-5) * (pmax + f32(scale))
+        w = pos - np.fmin(np.fmax(pos, np.asarray(vmin, f32)[None, :]), np.asarray(vmax, f32)[None, :])
+        db = np.sqrt((w[:, 0] * w[:, 0] + w[:, 1] * w[:, 1]) + w[:, 2] * w[:, 2])
+        rate = (d[:, 0] * w[:, 0] + d[:, 1] * w[:, 1]) + d[:, 2] * w[:, 2]
+        return (db > f32(1.00001) * (margin + f32(0.001))) & (rate >= f32(2e-5) * db)
+
+
 def idle_share(steps, max_steps, wave=64):
     """Share of lane-steps idle in waves of `wave` consecutive rays when every ray marches to its hit and a miss to
     max_steps (the arm without the early stop): 1 - sum(lane steps) / (wave x sum(the wave's longest lane))."""

@@ -554,6 +554,45 @@ def march_legs(args):
     print("wrote", args.out)
 
 
+def march_frame_legs(args):
+    """--march-frame: march_legs' frame leg alone -- the RT_ISECT_RAY_MARCH frame of the scene's camera at 1920x1080x1,
+    render_frame_device between events -- from this build and from --parent-lib, samples interleaved (measure)."""
+    mods = {"this": load("rtm_this", None)}
+    if args.parent_lib:
+        mods["parent"] = load("rtm_parent", args.parent_lib)
+    res = {"tool": "tools/bench_rays.py --march-frame", "frame": [W, H, 1], "launches_per_sample": args.steps,
+           "warmup": args.warmup, "samples": 5, "device": torch.cuda.get_device_name(0),
+           "arms": {k: m.library_build_hash() for k, m in mods.items()}, "scenes": {}}
+    st = torch.cuda.current_stream().cuda_stream
+    for sid in args.scenes:
+        hs = {k: m.HostScene.load(sid) for k, m in mods.items()}
+        gs = {k: m.GpuScene(hs[k], 0) for k, m in mods.items()}
+        outs = {k: torch.empty(W * H, dtype=torch.int32, device="cuda") for k in mods}
+        fms = {k: gs[k].frame(W, H, 1, intersector=m.RT_ISECT_RAY_MARCH) for k, m in mods.items()}
+        fr = measure({k: (lambda k=k: gs[k].render_frame_device(fms[k], outs[k].data_ptr(), st)) for k in mods},
+                     W * H, args.steps, args.warmup)
+        torch.cuda.synchronize()
+        entry = {"triangles": int(hs["this"].mesh()[1].shape[0]), **fr}
+        for k in fr:
+            fr[k]["unit"] = "samples/s"
+        if "parent" in fr:
+            entry["same_frame_as_parent"] = bool(torch.equal(outs["this"], outs["parent"]))
+            entry["this_over_parent_ms"] = round(fr["this"]["ms"] / fr["parent"]["ms"], 4)
+            entry["tie_within_spread"] = bool(abs(fr["this"]["ms"] - fr["parent"]["ms"]) <=
+                                              max(fr["this"]["spread"], fr["parent"]["spread"]) * fr["parent"]["ms"])
+        res["scenes"][str(sid)] = entry
+        print(json.dumps({str(sid): entry}), flush=True)
+        for g in gs.values():
+            g.close()
+        for h in hs.values():
+            h.close()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print("wrote", args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", type=int, nargs="+", default=[8, 1])
@@ -566,10 +605,14 @@ def main():
     ap.add_argument("--distance", action="store_true", help="the distance-query legs (distance_legs) instead of the ray legs")
     ap.add_argument("--march", action="store_true", help="the march-query legs (march_legs) instead of the ray legs; "
                                                         "--steps / --warmup default to 1 there: a launch is long")
+    ap.add_argument("--march-frame", action="store_true", help="the RT_ISECT_RAY_MARCH frame leg alone, this build beside "
+                                                              "--parent-lib (march_frame_legs); --out is required")
     ap.add_argument("--out", default=None, help="default: profiles/rays_bench.json (--occlusion: profiles/occlusion_bench.json; "
                                                 "--ao: profiles/ao_bench.json; --distance: profiles/distance_bench.json; --march: profiles/march_bench.json)")
     args = ap.parse_args()
-    if args.march:
+    if args.march_frame and args.out is None:
+        raise SystemExit("--march-frame needs --out")
+    if args.march or args.march_frame:
         args.steps = 1 if args.steps == ap.get_default("steps") else args.steps
         args.warmup = 1 if args.warmup == ap.get_default("warmup") else args.warmup
     if args.out is None:
@@ -577,6 +620,8 @@ def main():
                                 "occlusion_bench.json" if args.occlusion else "rays_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_rays.py measures on the GPU; none is visible")
+    if args.march_frame:
+        return march_frame_legs(args)
     if args.march:
         return march_legs(args)
     if args.distance:
