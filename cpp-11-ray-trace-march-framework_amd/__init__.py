@@ -26,7 +26,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 KERNEL_SOURCES = ("csrc/rt_kernels.hip", "csrc/rt_walk.h", "csrc/rt_kparams.h", "csrc/rt_plan.hip",
                   "csrc/rt_scene.h", "csrc/rt_tracer.hip", "csrc/rt_grid_build.hip", "csrc/rt_device.h",
                   "csrc/rt_internal.h", "csrc/rt_box_words.h", "csrc/rt_fref_slots.h", "csrc/rt_cam_bound.h", "csrc/rt_record_gate.h", "csrc/rt_setup_div.h", "csrc/rt_miss_mask.h", "csrc/rt_rays.hip",
-                  "csrc/rt_ray_common.h", "csrc/rt_occlusion.hip", "csrc/rt_ao.hip", "csrc/rt_distance.hip",
+                  "csrc/rt_ray_common.h", "csrc/rt_occlusion.hip", "csrc/rt_crossings.hip", "csrc/rt_ao.hip", "csrc/rt_distance.hip",
                   "csrc/rt_dist_tree.h", "csrc/rt_march.hip", "csrc/rt_dist_sweep.h", "csrc/rt_launch.hip", "csrc/rt_queries.hip", "csrc/rt_launch.h", "csrc/Makefile",
                   "../include/rt_tracer.h")
 
@@ -74,7 +74,7 @@ TRACER_SYMBOLS = [
     "rt_scene_create_from_mesh", "rt_kernel_times", "rt_render_frame_host", "rt_frame_host_wait", "rt_host_alloc",
     "rt_host_free", "rt_render_hits_device", "rt_scene_info_get", "rt_build_hash", "rt_render_batch_device",
     "rt_render_records_device", "rt_render_frame_host_tiled", "rt_fref_buffer_bytes",
-    "rt_trace_rays_device", "rt_primary_rays_device", "rt_occluded_rays_device",
+    "rt_trace_rays_device", "rt_primary_rays_device", "rt_occluded_rays_device", "rt_crossing_rays_device",
     "rt_ao_table", "rt_ao_rotations", "rt_render_ao_device", "rt_distance_points_device",
     "rt_march_rays_device", "rt_debug_miss_mask", "rt_debug_lane_launches",
 ]
@@ -140,6 +140,10 @@ class RayHit(ctypes.Structure):             # rt_ray_hit, 16 B
     _fields_ = [("tri", c_u32), ("t", c_f32), ("u", c_f32), ("v", c_f32)]
 
 
+class RayCross(ctypes.Structure):           # rt_ray_cross, 8 B
+    _fields_ = [("count", c_u32), ("front", c_u32)]
+
+
 class PointDistRec(ctypes.Structure):       # rt_point_dist, 8 B
     _fields_ = [("dist", c_f32), ("tri", c_u32)]
 
@@ -180,6 +184,15 @@ RAY_HIT_DTYPE = np.dtype([("tri", "<u4"), ("t", "<f4"), ("u", "<f4"), ("v", "<f4
 RAY_WORDS, RAY_HIT_WORDS, SAMPLE_REC_WORDS = 6, 4, 12     # 32-bit words of rt_ray, rt_ray_hit, rt_sample_rec
 # GpuScene.trace_rays' result: per-ray columns, the raw rt_ray_hit words and (count=True) the records
 RayHits = collections.namedtuple("RayHits", ["tri", "t", "u", "v", "hits", "rec"])
+# rt_ray_cross (rt_crossing_rays_device): the counted tests of a ray and those with det > 0
+RAY_CROSS_DTYPE = np.dtype([("count", "<u4"), ("front", "<u4")])
+RAY_CROSS_WORDS = 2
+# GpuScene.crossings' result: per-ray columns and the raw rt_ray_cross words
+Crossings = collections.namedtuple("Crossings", ["count", "front", "raw"])
+# GpuScene.inside's default directions: unit float32 vectors, none axis-aligned and none in a coordinate plane
+INSIDE_DIRS = np.array([[0.53811389, 0.72151864, 0.43571126],
+                        [-0.63672209, 0.30911073, 0.70642447],
+                        [0.21129724, -0.87288857, 0.43979424]], np.float32)
 # rt_point_dist (rt_distance_points_device): no triangle below FLT_MAX is dist FLT_MAX, tri 0xFFFFFFFF
 POINT_DIST_DTYPE = np.dtype([("dist", "<f4"), ("tri", "<u4")])
 POINT_WORDS, POINT_DIST_WORDS = 3, 2
@@ -244,6 +257,8 @@ def tracer_lib():
             L.rt_primary_rays_device.argtypes = [vp, ctypes.POINTER(Frame), vp, vp]
         if hasattr(L, "rt_occluded_rays_device"):    # absent in earlier builds (A/B runs)
             L.rt_occluded_rays_device.argtypes = [vp, vp, vp, c_u32, c_u32, vp, vp]
+        if hasattr(L, "rt_crossing_rays_device"):    # absent in earlier builds (A/B runs)
+            L.rt_crossing_rays_device.argtypes = [vp, vp, vp, c_u32, c_u32, vp, vp]
         if hasattr(L, "rt_render_ao_device"):        # absent in earlier builds (A/B runs)
             L.rt_ao_table.argtypes = [c_u32, vp]
             L.rt_ao_rotations.argtypes = [vp]
@@ -788,6 +803,13 @@ class GpuScene:
     def _stream(self, torch, stream):
         return torch.cuda.current_stream(self.device).cuda_stream if stream is None else int(stream)
 
+    def _torch_stream(self, torch, dev, stream):
+        """A context in which torch's operations run on `stream` (None: torch's current stream, unchanged)."""
+        import contextlib
+        if stream is None or int(stream) == torch.cuda.current_stream(dev).cuda_stream:
+            return contextlib.nullcontext()
+        return torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=dev))
+
     def primary_rays(self, frame, stream=None):
         """rt_primary_rays_device: the frame's width * height * spp camera rays in (y, x, sample) order
         as a torch float32 [n, 6] tensor (origin, direction) on the scene's device -- the bits the frames
@@ -859,16 +881,8 @@ class GpuScene:
         return RayHits(tri, hits[:, 1].view(torch.float32), hits[:, 2].view(torch.float32),
                        hits[:, 3].view(torch.float32), hits, rec)
 
-    def occluded(self, rays, tminmax=None, sort=False, stream=None):
-        """rt_occluded_rays_device: is anything hit inside the open interval (tmin, tmax) of each ray?  The
-        any-hit walk of include/rt_tracer.h: Grid::Intersect ended by the first test that counts, and by the
-        first step whose crossing time is >= tmax; t is in units of the direction as passed.
-
-        rays [n, 6] and tminmax [n, 2] (None: (-inf, +inf) for every ray): contiguous float32 torch CUDA tensors
-        on the scene's device, used in place through data_ptr(), asynchronously on `stream` as trace_rays does
-        -> a torch.uint8 [n] tensor of 1 / 0; or C-contiguous float32 numpy arrays, which are uploaded ->
-        a numpy bool [n] (synchronous).  The two inputs are of one kind.  Anything else raises ValueError before
-        any launch.  sort=True (RT_RAYS_SORT): the same bytes, the rays traced in sorted order."""
+    def _interval_rays(self, rays, tminmax):
+        """The argument checks occluded() and crossings() share: (host, n, device, d_rays, d_tminmax or None)."""
         import torch
         host = isinstance(rays, np.ndarray)
         if host:
@@ -897,6 +911,20 @@ class GpuScene:
             d_rays, d_tmm, dev = rays, tminmax, rays.device
         else:
             raise ValueError("rays: a torch CUDA tensor or a numpy array")
+        return host, n, dev, d_rays, d_tmm
+
+    def occluded(self, rays, tminmax=None, sort=False, stream=None):
+        """rt_occluded_rays_device: is anything hit inside the open interval (tmin, tmax) of each ray?  The
+        any-hit walk of include/rt_tracer.h: Grid::Intersect ended by the first test that counts, and by the
+        first step whose crossing time is >= tmax; t is in units of the direction as passed.
+
+        rays [n, 6] and tminmax [n, 2] (None: (-inf, +inf) for every ray): contiguous float32 torch CUDA tensors
+        on the scene's device, used in place through data_ptr(), asynchronously on `stream` as trace_rays does
+        -> a torch.uint8 [n] tensor of 1 / 0; or C-contiguous float32 numpy arrays, which are uploaded ->
+        a numpy bool [n] (synchronous).  The two inputs are of one kind.  Anything else raises ValueError before
+        any launch.  sort=True (RT_RAYS_SORT): the same bytes, the rays traced in sorted order."""
+        import torch
+        host, n, dev, d_rays, d_tmm = self._interval_rays(rays, tminmax)
         occ = torch.empty((n,), dtype=torch.uint8, device=dev)
         if stream is not None and int(stream) != torch.cuda.current_stream(dev).cuda_stream:
             occ.record_stream(torch.cuda.ExternalStream(int(stream), device=dev))     # (as trace_rays)
@@ -910,6 +938,110 @@ class GpuScene:
                 torch.cuda.synchronize(dev)            # the copy below runs on torch's stream
             return occ.cpu().numpy().astype(bool)
         return occ
+
+    def crossings(self, rays, tminmax=None, sort=False, stream=None):
+        """rt_crossing_rays_device: how many surfaces does each ray cross inside the open interval (tmin, tmax), and
+        how many of them against their normal?  The counting walk of include/rt_tracer.h: Grid::Intersect that ends
+        at no hit and counts a test in the one cell whose interval [entry crossing, exit crossing) holds it; t is in
+        units of the direction as passed.
+
+        rays, tminmax, sort, stream and the ValueErrors: as occluded().  Returns Crossings: count u32 [n] (the counted
+        tests), front u32 [n] (those with det > 0: the ray ran against e1 x e2), raw = the [n, 2] rt_ray_cross words
+        -- torch tensors on the rays' device (int32 bits where torch has no uint32), or numpy arrays for numpy
+        input (synchronous).  For a closed, consistently oriented mesh and a ray over (0, +inf), count - 2 front is 1
+        from a point inside and 0 from outside, and count & 1 is the parity test."""
+        import torch
+        host, n, dev, d_rays, d_tmm = self._interval_rays(rays, tminmax)
+        raw = torch.empty((n, RAY_CROSS_WORDS), dtype=torch.int32, device=dev)
+        if stream is not None and int(stream) != torch.cuda.current_stream(dev).cuda_stream:
+            raw.record_stream(torch.cuda.ExternalStream(int(stream), device=dev))     # (as trace_rays)
+        L = tracer_lib()
+        _check(L.rt_crossing_rays_device(self._h, ctypes.c_void_p(d_rays.data_ptr()),
+                                         ctypes.c_void_p(d_tmm.data_ptr() if d_tmm is not None and n else 0), n,
+                                         RT_RAYS_SORT if sort else 0, ctypes.c_void_p(raw.data_ptr()),
+                                         ctypes.c_void_p(self._stream(torch, stream))), L, "rt_crossing_rays_device")
+        if host:
+            if stream is not None:
+                torch.cuda.synchronize(dev)            # the copy below runs on torch's stream
+            r = raw.cpu().numpy().view(RAY_CROSS_DTYPE).reshape(n)
+            return Crossings(r["count"], r["front"], r)
+        u32 = getattr(torch, "uint32", None)
+        count, front = (raw[:, 0].view(u32), raw[:, 1].view(u32)) if u32 is not None else (raw[:, 0], raw[:, 1])
+        return Crossings(count, front, raw)
+
+    def inside(self, points, rule="winding", dirs=None, stream=None):
+        """Point-in-mesh classification of points [n, 3] by crossings(): from every point one ray per direction over
+        (0, +inf), all in ONE crossings call, and the majority of the directions' answers (formed by torch
+        operations on the device).  rule="winding": a direction says inside when count - 2 front > 0 (more
+        crossings along the normals than against them: right for a closed, consistently oriented mesh);
+        rule="parity": when count is odd (any closed mesh).
+
+        dirs: an odd number of directions as a float32 [k, 3] numpy array (used as passed), or None = INSIDE_DIRS,
+        the three fixed float32 unit vectors
+            ( 0.53811389,  0.72151864, 0.43571126)
+            (-0.63672209,  0.30911073, 0.70642447)
+            ( 0.21129724, -0.87288857, 0.43979424)
+        none axis-aligned and none in a coordinate plane, so no ray runs inside a grid plane or along the edges of an
+        axis-aligned mesh.  A point within float fuzz of the surface may fall either way.
+
+        points: as distance() takes them.  Returns a torch.bool [n] tensor on the points' device, or a numpy bool [n]
+        array for numpy input (synchronous).  Anything else raises ValueError before any launch."""
+        import torch
+        if rule not in ("winding", "parity"):
+            raise ValueError('rule: "winding" or "parity"')
+        d = INSIDE_DIRS if dirs is None else dirs
+        if (not isinstance(d, np.ndarray) or d.dtype != np.float32 or d.ndim != 2 or d.shape[1] != 3 or
+                d.shape[0] % 2 != 1 or not np.isfinite(d).all()):
+            raise ValueError("dirs: a finite float32 array of shape [k, 3], k odd")
+        host = isinstance(points, np.ndarray)
+        d_pts = self._points(points)
+        n, k, dev = d_pts.shape[0], d.shape[0], d_pts.device
+        if n * k >= 1 << 31:
+            raise ValueError("points x directions: below 2^31 rays")
+        with self._torch_stream(torch, dev, stream):      # the ray set-up and the vote run where the walk does
+            # ray j * n + i: point i along direction j
+            rays = torch.empty((k, n, RAY_WORDS), dtype=torch.float32, device=dev)
+            rays[:, :, :3] = d_pts
+            rays[:, :, 3:] = torch.from_numpy(np.ascontiguousarray(d)).to(dev)[:, None, :]
+            tmm = torch.tensor([0.0, float("inf")], dtype=torch.float32, device=dev).repeat(n * k, 1)
+            c = self.crossings(rays.view(n * k, RAY_WORDS), tmm, stream=stream)
+            count, front = c.raw[:, 0].view(k, n), c.raw[:, 1].view(k, n)   # int32 words: counts are far below 2^31
+            yes = (count - 2 * front) > 0 if rule == "winding" else (count & 1) != 0
+            res = yes.sum(dim=0) * 2 > k
+            return res.cpu().numpy() if host else res
+
+    def signed_distance(self, points, closest=False, exhaustive=False, sort=False, rule="winding", dirs=None,
+                        stream=None):
+        """distance() with a sign: PointDist whose dist is negated where inside(points, rule, dirs) -- tri, closest
+        and raw are distance()'s, and abs(dist) is distance()'s dist bit for bit.  Arguments as distance() and
+        inside()."""
+        import torch
+        ins = self.inside(points, rule=rule, dirs=dirs, stream=stream)      # (first: its ValueErrors before any launch)
+        pd = self.distance(points, closest=closest, exhaustive=exhaustive, sort=sort, stream=stream)
+        if isinstance(points, np.ndarray):
+            return PointDist(np.where(ins, -pd.dist, pd.dist), pd.tri, pd.closest, pd.raw)
+        with self._torch_stream(torch, pd.dist.device, stream):
+            return PointDist(torch.where(ins, -pd.dist, pd.dist), pd.tri, pd.closest, pd.raw)
+
+    def _points(self, points):
+        """The argument checks distance() and inside() share: the points on the scene's device."""
+        import torch
+        if isinstance(points, np.ndarray):
+            if (points.dtype != np.float32 or points.ndim != 2 or points.shape[1] != POINT_WORDS or
+                    not points.flags["C_CONTIGUOUS"]):
+                raise ValueError("points: a C-contiguous float32 array of shape [n, 3]")
+            d_pts = torch.from_numpy(points).to(f"cuda:{self.device}")
+        elif isinstance(points, torch.Tensor):
+            if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != POINT_WORDS:
+                raise ValueError("points: a float32 tensor of shape [n, 3]")
+            if not points.is_cuda or points.device.index != self.device:
+                raise ValueError(f"points: a tensor on cuda:{self.device} (host memory is not read in place)")
+            if not points.is_contiguous():
+                raise ValueError("points: a contiguous tensor (a strided view would be read as other points)")
+            d_pts = points
+        else:
+            raise ValueError("points: a torch CUDA tensor or a numpy array")
+        return d_pts
 
     def distance(self, points, closest=False, exhaustive=False, sort=False, stream=None):
         """rt_distance_points_device: Renderer::DistanceBruteForce for caller-supplied points [n, 3] -- per point the
@@ -928,21 +1060,7 @@ class GpuScene:
         their position -- for points in no useful order.  Both give the same bytes, in input order."""
         import torch
         host = isinstance(points, np.ndarray)
-        if host:
-            if (points.dtype != np.float32 or points.ndim != 2 or points.shape[1] != POINT_WORDS or
-                    not points.flags["C_CONTIGUOUS"]):
-                raise ValueError("points: a C-contiguous float32 array of shape [n, 3]")
-            d_pts = torch.from_numpy(points).to(f"cuda:{self.device}")
-        elif isinstance(points, torch.Tensor):
-            if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != POINT_WORDS:
-                raise ValueError("points: a float32 tensor of shape [n, 3]")
-            if not points.is_cuda or points.device.index != self.device:
-                raise ValueError(f"points: a tensor on cuda:{self.device} (host memory is not read in place)")
-            if not points.is_contiguous():
-                raise ValueError("points: a contiguous tensor (a strided view would be read as other points)")
-            d_pts = points
-        else:
-            raise ValueError("points: a torch CUDA tensor or a numpy array")
+        d_pts = self._points(points)
         n = d_pts.shape[0]
         dev = d_pts.device
         raw = torch.empty((n, POINT_DIST_WORDS), dtype=torch.int32, device=dev)

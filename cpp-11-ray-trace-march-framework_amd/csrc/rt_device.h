@@ -149,17 +149,19 @@ __device__ __forceinline__ bool ray_tri_mt_pred(float ox, float oy, float oz, fl
 // checks (triangle.h:77-87) the q/v/t half is skipped for the whole wave.  A scalar branch
 // (s_cbranch on a ballot), not a divergent one; results identical to ray_tri_mt_pred.
 // FAST_RCP (rt_rays.hip only): inv_det by rcp_nr, as mt_rec_first -- the caller guarantees |det| < 2^126.
+// ray_tri_mt_gated_det also hands out det, the value triangle.h:48 forms and :77 tests (rt_crossings.hip reads
+// its sign); ray_tri_mt_gated drops it, and compiles to what it was without the extra result.
 template <bool FAST_RCP = false>
-__device__ __forceinline__ bool ray_tri_mt_gated(float ox, float oy, float oz, float dx, float dy, float dz,
-                                                 float v0x, float v0y, float v0z,
-                                                 float e1x, float e1y, float e1z,
-                                                 float e2x, float e2y, float e2z,
-                                                 float& t, float& u, float& v)
+__device__ __forceinline__ bool ray_tri_mt_gated_det(float ox, float oy, float oz, float dx, float dy, float dz,
+                                                     float v0x, float v0y, float v0z,
+                                                     float e1x, float e1y, float e1z,
+                                                     float e2x, float e2y, float e2z,
+                                                     float& t, float& u, float& v, float& det)
 {
     const float px = dy * e2z - dz * e2y;
     const float py = dz * e2x - dx * e2z;
     const float pz = dx * e2y - dy * e2x;
-    const float det = e1x * px + e1y * py + e1z * pz;
+    det = e1x * px + e1y * py + e1z * pz;
     const float inv_det = FAST_RCP ? rcp_nr(det) : 1.0f / det;
     const float tx = ox - v0x, ty = oy - v0y, tz = oz - v0z;
     u = (tx * px + ty * py + tz * pz) * inv_det;
@@ -171,6 +173,17 @@ __device__ __forceinline__ bool ray_tri_mt_gated(float ox, float oy, float oz, f
     v = (dx * qx + dy * qy + dz * qz) * inv_det;
     t = (e2x * qx + e2y * qy + e2z * qz) * inv_det;
     return ok1 & !(v < 0.0f || u + v > 1.0f) & (t >= 0.0f);
+}
+template <bool FAST_RCP = false>
+__device__ __forceinline__ bool ray_tri_mt_gated(float ox, float oy, float oz, float dx, float dy, float dz,
+                                                 float v0x, float v0y, float v0z,
+                                                 float e1x, float e1y, float e1z,
+                                                 float e2x, float e2y, float e2z,
+                                                 float& t, float& u, float& v)
+{
+    float det;
+    return ray_tri_mt_gated_det<FAST_RCP>(ox, oy, oz, dx, dy, dz, v0x, v0y, v0z, e1x, e1y, e1z, e2x, e2y, e2z, t, u, v,
+                                          det);
 }
 
 // Per-camera record of one CSR reference for rays that share one origin (every primary ray of

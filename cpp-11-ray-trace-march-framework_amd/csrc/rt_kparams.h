@@ -55,6 +55,10 @@ constexpr int kVarRays = 8388608;           // rt_trace_rays_device (rt_rays.hip
 constexpr int kVarAnyHit = 16777216;        // rt_occluded_rays_device (rt_occlusion.hip), only with kVarRays: the walk
                                             // ends at the first test that counts inside (tmin, tmax) and at the first
                                             // step whose crossing is >= tmax (grid_intersect); no t, u, v, tri
+constexpr int kVarCross = 33554432;         // rt_crossing_rays_device (rt_crossings.hip), only with kVarRays and never
+                                            // with kVarAnyHit: the walk counts every test inside (tmin, tmax) that lies
+                                            // in its cell's own interval [entry crossing, exit crossing) and ends only
+                                            // at the any-hit walk's step rule or the grid's end (grid_intersect)
 // AUTO's traversal: every feature above that is exact for every scene ...
 constexpr int kVarAutoCore = kVarWaveGate | kVarDistSkip | kVarOriginPre | kVarXcdBands | kVarUniform;
 // ... plus the two that need a scene property (rt_scene::rcp_safe, rt_scene::pack_ok)
@@ -369,6 +373,10 @@ uint32_t ray_key_bits();                        // ... which are sorted by this 
 // kVarAnyHit; tminmax null: (-inf, +inf) for every ray
 using occluded_fn = void (*)(KParams, const float2 *, const float2 *, const unsigned long long *, uint32_t, uint8_t *);
 occluded_fn occluded_rays_kernel(int var);
+// rt_crossings.hip: k_cross_rays<var>(P, rays, tminmax, order, n, out) -- var: k_trace_rays' fast-arm variant |
+// kVarCross; out[i] = {count, front} (rt_ray_cross, one 8-byte store); tminmax null: (-inf, +inf) for every ray
+using cross_fn = void (*)(KParams, const float2 *, const float2 *, const unsigned long long *, uint32_t, uint2 *);
+cross_fn cross_rays_kernel(int var);
 // rt_ao.hip: k_render_ao<var>(KAo) -- var: k_trace_rays' fast-arm variant (the AO rays take it | kVarAnyHit).  The
 // frame's KParams and the AO parameters are ONE kernel argument, so the directions and rotations are read from
 // the kernarg segment by scalar loads (and re-read after the walks, as late_params does it).

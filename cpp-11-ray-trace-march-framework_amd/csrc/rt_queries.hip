@@ -1,8 +1,8 @@
 // rt_queries.hip -- the query entry points of librt_tracer.so (include/rt_tracer.h): per-sample records of a frame
 // rectangle (rt_trace_samples), caller-supplied rays (rt_trace_rays_device), occlusion (rt_occluded_rays_device),
-// point distances (rt_distance_points_device), marches (rt_march_rays_device), a frame's primary rays
-// (rt_primary_rays_device) and AO frames (rt_render_ao_device).  Kernels: rt_kernels.hip, rt_rays.hip,
-// rt_occlusion.hip, rt_distance.hip, rt_march.hip, rt_ao.hip.
+// crossings (rt_crossing_rays_device), point distances (rt_distance_points_device), marches (rt_march_rays_device), a
+// frame's primary rays (rt_primary_rays_device) and AO frames (rt_render_ao_device).  Kernels: rt_kernels.hip,
+// rt_rays.hip, rt_occlusion.hip, rt_crossings.hip, rt_distance.hip, rt_march.hip, rt_ao.hip.
 // What they share with the render launches (rt_launch.hip) is declared in rt_launch.h.
 
 #include <hip/hip_runtime.h>
@@ -221,6 +221,46 @@ int rt_occluded_rays_device(rt_scene *s, const rt_ray *d_rays, const float *d_tm
     unsigned long long *sorted = nullptr;
     if (int rc = rays_sorted_order(s, P, rays, n, st, &sorted)) return rc;
     hipLaunchKernelGGL(fn, grid, wg, 0, st, P, rays, tmm, static_cast<const unsigned long long *>(sorted), n, d_occluded);
+    RT_HIP(hipGetLastError());
+    return rays_sorted_done(s, st);
+}
+
+// d_out[i] = what the counting walk over (tmin, tmax) leaves for ray i (include/rt_tracer.h; kernels:
+// rt_crossings.hip).  Everything but the output record is rt_occluded_rays_device's.
+int rt_crossing_rays_device(rt_scene *s, const rt_ray *d_rays, const float *d_tminmax, uint32_t n, uint32_t flags,
+                            rt_ray_cross *d_out, void *hip_stream)
+{
+    if (!s) return fail(RT_E_INVALID, "scene is NULL");
+    if (flags & RT_RAYS_COUNT) return fail(RT_E_INVALID, "RT_RAYS_COUNT: the crossing walk has no record arm");
+    if (flags & ~uint32_t(RT_RAYS_SORT)) return fail(RT_E_INVALID, "unknown rt_rays_flags bit");
+    const bool sort = (flags & RT_RAYS_SORT) != 0u;
+    if (n >= 0x80000000u) return fail(RT_E_INVALID, "n must be below 2^31");
+    if (n == 0) return RT_OK;
+    if (!d_rays) return fail(RT_E_INVALID, "d_rays is NULL");
+    if (!d_out) return fail(RT_E_INVALID, "d_out is NULL");
+    if ((uintptr_t(d_rays) | uintptr_t(d_tminmax) | uintptr_t(d_out)) & 7u)
+        return fail(RT_E_INVALID, "d_rays, d_tminmax and d_out must be 8-byte aligned");
+    if (int rc = ensure_device(s)) return rc;
+    KParams P;
+    query_params(s, P);
+    const int var = kVarCross | kVarRays | kVarWaveGate | kVarDistSkip | scene_traversal_bits(s);
+    const cross_fn fn = cross_rays_kernel(var);
+    if (!fn) return fail(RT_E_INVALID, "kernel variant not built: " + std::to_string(var));
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const float2 *rays = reinterpret_cast<const float2 *>(d_rays);
+    const float2 *tmm = reinterpret_cast<const float2 *>(d_tminmax);
+    uint2 *out = reinterpret_cast<uint2 *>(d_out);
+    const dim3 grid((n + kWG - 1) / kWG), wg(kWG);
+    if (!sort)
+    {
+        hipLaunchKernelGGL(fn, grid, wg, 0, st, P, rays, tmm, static_cast<const unsigned long long *>(nullptr), n, out);
+        RT_HIP(hipGetLastError());
+        return RT_OK;
+    }
+    std::lock_guard<std::mutex> lk(s->mtx);
+    unsigned long long *sorted = nullptr;
+    if (int rc = rays_sorted_order(s, P, rays, n, st, &sorted)) return rc;
+    hipLaunchKernelGGL(fn, grid, wg, 0, st, P, rays, tmm, static_cast<const unsigned long long *>(sorted), n, out);
     RT_HIP(hipGetLastError());
     return rays_sorted_done(s, st);
 }

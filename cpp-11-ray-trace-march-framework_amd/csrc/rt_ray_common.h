@@ -1,5 +1,6 @@
 // rt_ray_common.h -- what the ray-query translation units share (rt_rays.hip: rt_trace_rays_device;
-// rt_occlusion.hip: rt_occluded_rays_device; rt_ao.hip: rt_render_ao_device) beside rt_walk.h's walk.
+// rt_occlusion.hip: rt_occluded_rays_device; rt_crossings.hip: rt_crossing_rays_device; rt_ao.hip:
+// rt_render_ao_device) beside rt_walk.h's walk.
 #pragma once
 #include "rt_cam_bound.h"
 #include "rt_walk.h"
@@ -53,6 +54,17 @@ __device__ __forceinline__ bool occlusion_walk(const KParams& P, float ox, float
     uint32_t tri = rtd::kNoTri, voxel = rtd::kNoTri, steps = 0, tests = 0;
     return grid_intersect<false, RT_TRI_MOLLER_TRUMBORE, VAR>(P, ox, oy, oz, dx, dy, dz, t, u, v, tri, voxel, steps, tests,
                                                               tmin);
+}
+
+// The counting walk of one ray over (tmin, tmax) (k_cross_rays): VAR carries kVarCross; count and front enter as 0
+template <int VAR>
+__device__ __forceinline__ void crossing_walk(const KParams& P, float ox, float oy, float oz, float dx, float dy, float dz,
+                                              float tmin, float tmax, uint32_t& count, uint32_t& front)
+{
+    float t = tmax, u = 0.0f, v = 0.0f;            // t carries tmax into the walk (grid_intersect)
+    uint32_t voxel = rtd::kNoTri, steps = 0;
+    (void)grid_intersect<false, RT_TRI_MOLLER_TRUMBORE, VAR>(P, ox, oy, oz, dx, dy, dz, t, u, v, count, voxel, steps, front,
+                                                             tmin);
 }
 
 } // namespace

@@ -216,7 +216,7 @@ template <bool STATS, int TRI, int VAR>
 __device__ __forceinline__ bool test_cell(const KParams& P, float ox, float oy, float oz, float dx, float dy,
                                           float dz, uint32_t kb, uint32_t ke, float nct_ax, float& t,
                                           float& u, float& v, uint32_t& tri, uint32_t& tests, uint32_t& lpar,
-                                          float tmin = 0.0f)
+                                          float tmin = 0.0f, float t_in = 0.0f)
 {
     constexpr bool PRE = (VAR & kVarOriginPre) != 0 && TRI == RT_TRI_MOLLER_TRUMBORE;
     constexpr bool F = (VAR & kVarFastRcp) != 0;
@@ -228,7 +228,14 @@ __device__ __forceinline__ bool test_cell(const KParams& P, float ox, float oy, 
     static_assert(!SPLIT || (PRE && !STATS), "the LDS tier runs AUTO's record test");
     static_assert(!ANY || ((VAR & kVarRays) != 0 && (VAR & kVarWaveGate) != 0 && !PRE && !STATS &&
                            TRI == RT_TRI_MOLLER_TRUMBORE), "the any-hit walk is the ray queries' fast arm");
+    // kVarCross (rt_crossing_rays_device): t holds tmax as above; a test counts when it lies in (tmin, tmax) AND in
+    // the cell's own interval [t_in, nct_ax), t_in the crossing the walk took into this cell.  Every counted test
+    // adds one to tri (the ray's count) and, where det > 0, one to tests (its front count); nothing ends the list.
+    constexpr bool CROSS = (VAR & kVarCross) != 0;
+    static_assert(!CROSS || (!ANY && (VAR & kVarRays) != 0 && (VAR & kVarWaveGate) != 0 && !PRE && !STATS &&
+                             TRI == RT_TRI_MOLLER_TRUMBORE), "the counting walk is the ray queries' fast arm");
     (void)lpar;
+    (void)t_in;
     // wave-uniform, and the same in every wave of the workgroup (their lanes and lists are the same)
     bool split = false;
     if constexpr (SPLIT) split = __any(ke - kb >= kLdsSplitMin);
@@ -475,6 +482,24 @@ __device__ __forceinline__ bool test_cell(const KParams& P, float ox, float oy, 
             ke = counted ? 0u : ke;
         }
         return counted;
+    }
+    else if constexpr (CROSS)
+    {
+        // The whole list in order: hit, t_in <= cur_t (the one inclusive bound), cur_t < nct_ax, tmin < cur_t and
+        // cur_t < tmax (tb as above; a NaN t_in or nct_ax counts nothing, as the compare itself).  det is the
+        // test's own (triangle.h:48), read only where the test counted.
+        for (uint32_t k = kb; k < ke; k++)
+        {
+            const float4 *rp = P.refs + size_t(k) * 3;
+            const float4 r0 = rp[0], r1 = rp[1], r2 = rp[2];
+            float ct = 0.0f, cu, cv, det;
+            const bool hit = rtd::ray_tri_mt_gated_det<F>(ox, oy, oz, dx, dy, dz, r0.x, r0.y, r0.z, r0.w, r1.x, r1.y,
+                                                          r1.z, r1.w, r2.x, ct, cu, cv, det);
+            const bool counted = hit & (t_in <= ct) & (ct < tb) & (tmin < ct);
+            tri += counted ? 1u : 0u;
+            tests += (counted & (det > 0.0f)) ? 1u : 0u;
+        }
+        return false;
     }
     else
     for (uint32_t k = kb; k < ke; k++)
@@ -870,11 +895,22 @@ __device__ __forceinline__ bool grid_intersect(const KParams& P, float ox, float
     // crossing stops nothing).  Both exits only end the walk sooner, and nothing is indexed by tmin or tmax:
     // the arguments on termination and on `cell` below hold unchanged.  t, u, v, tri, voxel are not written.
     constexpr bool ANY = (VAR & kVarAnyHit) != 0;
+    // kVarCross (rt_crossing_rays_device): the any-hit walk's interval and step rule, but a counted test ends
+    // nothing, and each looked-up cell is tested against its own interval [t_in, exit crossing): t_in is the
+    // crossing of the last step taken before the cell (-inf before the first), which every arm below hands on --
+    // the plain arms from the advance of the iteration before, the box runs from the run's last bare step.  The
+    // crossings a walk takes never decrease, so the intervals are disjoint and a (ray, triangle) pair listed in
+    // several cells counts in at most one.  The counts leave in tri (count) and tests (front), which enter as 0;
+    // the return value is false and t, u, v are not written.
+    constexpr bool CROSS = (VAR & kVarCross) != 0;
+    constexpr bool IVAL = ANY || CROSS;                 // the walks over (tmin, tmax)
     float tmax = 0.0f;
-    if constexpr (ANY) tmax = t;
+    if constexpr (IVAL) tmax = t;
     bool found = false;                 // kVarAnyHit: the walk's result
+    float t_in = -__builtin_inff();     // kVarCross: the crossing into the cell about to be tested
     (void)tmax;
     (void)found;
+    (void)t_in;
     float nct0, nct1, nct2, dt0, dt1, dt2;
     int rem0, rem1, rem2, cs0, cs1, cs2, cell;
     // (the ray-query walk with the Newton 1/det but without packed counts: its kernel stands at 63 VGPRs and
@@ -887,7 +923,7 @@ __device__ __forceinline__ bool grid_intersect(const KParams& P, float ox, float
     if (!dda_setup<RCP_SETUP>(P, ox, oy, oz, dx, dy, dz, nct0, nct1, nct2, dt0, dt1, dt2, rem0, rem1, rem2, cs0, cs1,
                               cs2, cell))
         return false;
-    if constexpr (!ANY) t = rtd::kFltMax;
+    if constexpr (!IVAL) t = rtd::kFltMax;
     uint32_t lpar = 0u;                 // kVarLdsSplit: the reduction buffers' parity (test_cell)
 
     if constexpr ((VAR & kVarSkipRun) != 0 && (VAR & kVarPackedRem) != 0)
@@ -952,15 +988,16 @@ __device__ __forceinline__ bool grid_intersect(const KParams& P, float ox, float
             }
             RT_DDA_ADVANCE_BOX(nct_ax, more);
             bool hit = false;
-            if (kb < ke) hit = test_cell<STATS, TRI, VAR>(P, ox, oy, oz, dx, dy, dz, kb, ke, nct_ax, t, u, v, tri, tests, lpar, tmin);
+            if (kb < ke) hit = test_cell<STATS, TRI, VAR>(P, ox, oy, oz, dx, dy, dz, kb, ke, nct_ax, t, u, v, tri, tests, lpar, tmin, t_in);
             // kVarAnyHit: the step just taken -- out of a looked-up cell -- crossed at nct_ax; a lane that stops
             // here takes no run (its box counts are dead: a set guard keeps it out)
             [[maybe_unused]] bool stop = false;
-            if constexpr (ANY)
+            if constexpr (IVAL)
             {
                 found = hit;
                 stop = nct_ax >= tmax;
                 boxw = stop ? kRemGuards : boxw;
+                t_in = nct_ax;          // kVarCross: the next looked-up cell's entry, unless a run steps on
             }
             const bool inside = (uint32_t(boxw) & uint32_t(kRemGuards)) == 0u;
             if (!sync && inside)
@@ -985,7 +1022,7 @@ __device__ __forceinline__ bool grid_intersect(const KParams& P, float ox, float
                 while (nct1 < tl && c1 < f1) { nct1 += dt1; c1++; }
                 while (nct2 < tl && c2 < f2) { nct2 += dt2; c2++; }
                 boxw -= c0 + (c1 << 11) + (c2 << 22);
-                if constexpr (ANY)
+                if constexpr (IVAL)
                 {
                     // Rule 3 of the any-hit walk asks after EVERY step whether its crossing was >= tmax; inside
                     // an empty box nothing is tested, so only the cell the run arrives at needs the answer: was
@@ -993,11 +1030,15 @@ __device__ __forceinline__ bool grid_intersect(const KParams& P, float ox, float
                     // minimum of three add chains with dt >= 0), the add chains above take only crossings below
                     // tl, and every bare step's crossing is an untaken one, >= tl: the LAST bare step's
                     // crossing is the run's largest, and it alone is compared.
+                    // kVarCross: the same value is the crossing into the cell the run arrives at -- the last
+                    // step taken before it -- and so that cell's t_in.  (It is a term of an add chain, not
+                    // recoverable from the state after the step as nct - dt.)
                     float last;
                     do
                         RT_DDA_BOX_BARE_STEP_T(last);
                     while ((uint32_t(boxw) & uint32_t(kRemGuards)) == 0u);
                     stop = last >= tmax;
+                    t_in = last;
                 }
                 else
                 do
@@ -1039,10 +1080,10 @@ __device__ __forceinline__ bool grid_intersect(const KParams& P, float ox, float
                 cell += int(d & 2047u) * cs0 + int((d >> 11) & 2047u) * cs1 + int(d >> 22) * cs2;
                 more = (remp & kRemGuards) == 0;
             }
-            if constexpr (ANY) more &= !stop;
+            if constexpr (IVAL) more &= !stop;
             if (hit | !more) break;
         }
-        if constexpr (ANY) return found;
+        if constexpr (IVAL) return found;
         // records only: the exit cell in the ray's box-word copy (trace_sample removes the copy's
         // offset, so nothing extra is live across the walk)
         voxel = exit_voxel(remp, cell, cs0, cs1, cs2);
@@ -1084,13 +1125,16 @@ __device__ __forceinline__ bool grid_intersect(const KParams& P, float ox, float
             // below), and the result read from t after the loop: the walk's loop-carried state
             // stays in VGPRs instead of per-exit lane masks (SALU per wave, PMC-measured)
             bool hit = false;
-            if (kb < ke) hit = test_cell<STATS, TRI, VAR>(P, ox, oy, oz, dx, dy, dz, kb, ke, nct_ax, t, u, v, tri, tests, lpar, tmin);
+            if (kb < ke) hit = test_cell<STATS, TRI, VAR>(P, ox, oy, oz, dx, dy, dz, kb, ke, nct_ax, t, u, v, tri, tests, lpar, tmin, t_in);
             bool done = hit | !more;
-            if constexpr (ANY)
+            if constexpr (IVAL)
             {
-                // (one cell per iteration here: every step's crossing is seen)
+                // (one cell per iteration here: every step's crossing is seen, and is the next cell's t_in.  The
+                // wave-uniform empty run below belongs to the bits that took the box-run arm above: no interval
+                // walk reaches it)
                 found = hit;
                 done |= nct_ax >= tmax;
+                t_in = nct_ax;
             }
             if constexpr ((VAR & kVarSkipRun) != 0 && (VAR & kVarPackedRem) != 0 && !STATS)
             {
@@ -1138,7 +1182,7 @@ __device__ __forceinline__ bool grid_intersect(const KParams& P, float ox, float
             }
             if (done) break;
         }
-        if constexpr (ANY) return found;
+        if constexpr (IVAL) return found;
         // a lane leaving the grid inside a block of bare steps stepped on: its last cell is lost
         if constexpr (!STATS)
         {
@@ -1160,11 +1204,14 @@ __device__ __forceinline__ bool grid_intersect(const KParams& P, float ox, float
         float nct_ax;
         bool more;
         RT_DDA_ADVANCE_ADD(nct_ax, more);
-        if (kb < ke && test_cell<STATS, TRI, VAR>(P, ox, oy, oz, dx, dy, dz, kb, ke, nct_ax, t, u, v, tri, tests, lpar, tmin))
+        if (kb < ke && test_cell<STATS, TRI, VAR>(P, ox, oy, oz, dx, dy, dz, kb, ke, nct_ax, t, u, v, tri, tests, lpar, tmin, t_in))
             return true;
         if (!more) break;
-        if constexpr (ANY)
+        if constexpr (IVAL)
+        {
             if (nct_ax >= tmax) break;
+            t_in = nct_ax;
+        }
     }
     if constexpr (!STATS) voxel = uint32_t(cell - (rem0 < 0 ? cs0 : (rem1 < 0 ? cs1 : cs2)));   // records only
     return false;

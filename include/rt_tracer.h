@@ -370,6 +370,48 @@ int  rt_trace_rays_device(rt_scene *scene, const rt_ray *d_rays, uint32_t n, uin
  * wrote are read, and it needs no ordering against the scene's render launches.  DESIGN.md §4.29 */
 int  rt_occluded_rays_device(rt_scene *scene, const rt_ray *d_rays, const float *d_tminmax, uint32_t n,
                              uint32_t flags, uint8_t *d_occluded, void *hip_stream);
+/* Crossing queries (point-in-mesh tests, the sign of a distance field, thickness, layer counts): how many surfaces
+ * does ray i cross inside the open interval (tmin, tmax), and how many of them against their normal?  One record
+ * per ray, d_out[i] = {count, front}, in input order; exactly n records are written.
+ * d_tminmax: [n][2] floats (tmin, tmax) per ray, 8-byte aligned, or NULL = (-inf, +inf) for every ray.
+ *
+ * d_out[i] is what this walk leaves for ray i.  It is Grid::Intersect (grid.cpp:159-281) with IntersectRayTri
+ * (triangle.h:15-107), unchanged but for these points:
+ *   0. t_in = -inf before the first cell; count = front = 0;
+ *   1. a test counts iff  hit && t_in <= cur_t && cur_t < next_crossing_t[step_axis] && tmin < cur_t && cur_t < tmax:
+ *      the occlusion walk's condition 1 plus the one inclusive lower bound.  No closer-than-previous clause;
+ *   2. a counted test does count += 1, and front += 1 when det > 0 -- det the f32 value triangle.h:48 forms and tests
+ *      against its epsilon; det > 0 means the ray runs against e1 x e2.  Nothing ends the list or the walk, and no
+ *      minimum is formed;
+ *   3. after the cell's list, before the advance (grid.cpp:274): if (next_crossing_t[step_axis] >= tmax) the walk
+ *      ends -- the occlusion walk's rule 3, the same compare on the same value; a NaN crossing ends nothing.
+ *      Otherwise t_in = next_crossing_t[step_axis], the value before += delta_t; then the reference's advance runs,
+ *      and leaving the grid ends the walk.
+ * Everything else is the reference's: the box entry, ToVoxel, the crossing times, cell order, list order, d used as
+ * passed (NOT normalised), the absolute 1e-8 det gate, t >= 0.  Hence:
+ *   - at most once.  The crossing times a walk takes never decrease (each is the minimum of three add chains with
+ *     dt >= 0), so the cells' intervals [t_in, next_crossing) are disjoint, so a (ray, triangle) pair counts in at
+ *     most one cell however many cells list the triangle: count <= B, B the number of mesh triangles whose
+ *     IntersectRayTri hit lies in (tmin, tmax).  The same holds for front and the hits with det > 0;
+ *   - count >= 1 implies rt_occluded_rays_device says 1 for the same ray and interval: a counted test meets that
+ *     walk's condition 1 in the same cell, and rule 3 is identical in both walks.  The converse can fail, and so can
+ *     "a closest hit implies count >= 1": a hit whose cur_t lies below its cell's t_in is accepted by the reference
+ *     but belongs to no interval;
+ *   - count == B except for float fuzz at cell planes: a triangle whose cur_t falls into the interval of a cell that
+ *     does not list it is not counted.  This is a definition, as the occlusion walk's converse is;
+ *   - winding: for a closed, consistently oriented mesh and a ray from p over (0, +inf), (count - front) - front is
+ *     1 when p is inside and 0 when it is outside, and count & 1 is the parity test;
+ *   - {0, 0} without a walk: a ray with any non-finite component, a NaN tmin or tmax, !(tmin < tmax), a ray that
+ *     misses the grid box.  -inf and +inf are legal bounds.
+ * flags: 0 or RT_RAYS_SORT (the same sort, scratch and serialisation as rt_trace_rays_device; the same bytes in
+ * input order).  RT_RAYS_COUNT or an unknown bit: RT_E_INVALID, nothing written.  Otherwise the argument rules
+ * are rt_trace_rays_device's: n == 0 is RT_OK and writes nothing, n < 2^31, NULL or misaligned d_rays, a
+ * misaligned d_tminmax and a NULL or misaligned d_out (8 bytes) are RT_E_INVALID before any launch.  Asynchronous
+ * on hip_stream.  Without RT_RAYS_SORT the call is stateless: no lock, no event, no allocation, only arrays
+ * rt_scene_create wrote are read, and it needs no ordering against the scene's render launches.  DESIGN.md §4.36 */
+typedef struct rt_ray_cross { uint32_t count; uint32_t front; } rt_ray_cross;   /* 8 B */
+int  rt_crossing_rays_device(rt_scene *scene, const rt_ray *d_rays, const float *d_tminmax, uint32_t n,
+                             uint32_t flags, rt_ray_cross *d_out, void *hip_stream);
 /* The frame's width * height * spp camera rays in (y, x, sample) order into d_rays: origin and direction
  * exactly as the render kernels form them (GenerateRay, camera.h:8-47, over the frame's tables), i.e. the
  * bits the frames are traced with -- the start of a bounce.  A launch of the scene like a render call

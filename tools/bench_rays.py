@@ -37,6 +37,7 @@ loop of GpuScene.distance calls it replaces, RT_MARCH_EXHAUSTIVE, the other seed
     python3 tools/bench_rays.py --occlusion
     python3 tools/bench_rays.py --ao
     python3 tools/bench_rays.py --distance
+    python3 tools/bench_rays.py --crossings
     tools/build_variant.sh seedmorton -DRT_MARCH_SEED=0 && tools/build_variant.sh nostop -DRT_MARCH_STOP=0 &&
         python3 tools/bench_rays.py --march --ab-lib seed_morton=librt_tracer_seedmorton.so --ab-lib no_stop=librt_tracer_nostop.so
 """
@@ -429,6 +430,125 @@ def distance_legs(args):
     print("wrote", args.out)
 
 
+def torch_brute_crossings(rays, tmin, tmax, v0, v1, v2, chunk=512):
+    """What a caller has without GpuScene.crossings: IntersectRayTri's formulas over rays x triangles in float32 torch,
+    `chunk` rays at a time, the hits inside (tmin, tmax) summed -> (count, front) int64.  torch fuses and orders the
+    sums as it likes, so the counts are NOT the walk's on rays that graze an edge."""
+    e1, e2 = v1 - v0, v2 - v0
+    cnt = torch.empty(rays.shape[0], dtype=torch.int64, device=rays.device)
+    fr = torch.empty_like(cnt)
+    for i in range(0, rays.shape[0], chunk):
+        o, d = rays[i:i + chunk, None, :3], rays[i:i + chunk, None, 3:]
+        p = torch.cross(d.expand(-1, e2.shape[0], -1), e2[None].expand(o.shape[0], -1, -1), dim=2)
+        det = (e1[None] * p).sum(2)
+        inv = 1.0 / det
+        tv = o - v0[None]
+        u = (tv * p).sum(2) * inv
+        q = torch.cross(tv, e1[None].expand(o.shape[0], -1, -1), dim=2)
+        v = (d * q).sum(2) * inv
+        t = (e2[None] * q).sum(2) * inv
+        hit = (det.abs() >= 1e-8) & (u >= 0) & (u <= 1) & (v >= 0) & (u + v <= 1) & (t >= 0) & (t > tmin) & (t < tmax)
+        cnt[i:i + chunk] = hit.sum(1)
+        fr[i:i + chunk] = (hit & (det > 0)).sum(1)
+    return cnt, fr
+
+
+def crossing_legs(args):
+    """--crossings: rt_crossing_rays_device (GpuScene.crossings) into profiles/crossings_bench.json.
+      Rays: the 1920x1080x4 camera rays shuffled (PCG64(41)) over the infinite interval, and the ambient-occlusion
+      bounce of the ray legs over (1e-4 box diagonals, +inf).  Arms, samples interleaved (measure): crossings, and
+      occluded on the same rays and interval -- the floor: that walk stops at its first counted test and this one
+      cannot (`ratio` = crossings ms / occluded ms; not a pass condition) -- and a chunked float32 torch brute force
+      over all triangles (torch_brute_crossings: what a caller has today; timed over the leg's first TORCH_RAYS rays).
+      `implies`: count >= 1 implies occluded on every ray (include/rt_tracer.h).
+      Points: the hit points of the 1920x1080x1 primary rays jittered by a normal of 1 % of the box diagonal (seed 47;
+      distance_legs' points): inside (three directions per point, one crossings call, the vote in torch) and
+      signed_distance beside distance() alone."""
+    TORCH_RAYS = 1 << 15
+    rtm = load("rtm_this", None)
+    res = {"tool": "tools/bench_rays.py --crossings", "frame": [W, H, SPP], "steps": args.steps, "warmup": args.warmup,
+           "samples": 5, "build_hash": rtm.library_build_hash(), "device": torch.cuda.get_device_name(0),
+           "torch_arm": f"chunked float32 brute force over the first {TORCH_RAYS} rays of a leg; not bit-exact", "scenes": {}}
+    st = torch.cuda.current_stream().cuda_stream
+    n = W * H * SPP
+    for sid in args.scenes:
+        hs = rtm.HostScene.load(sid)
+        gs = rtm.GpuScene(hs, 0)
+        rays = gs.primary_rays(gs.frame(W, H, SPP))
+        v, t = hs.mesh()
+        pos = torch.from_numpy(np.ascontiguousarray(v[:, :3])).cuda()
+        idx = torch.from_numpy(np.ascontiguousarray(t[:, :3]).astype(np.int64)).cuda()
+        v0, v1, v2 = pos[idx[:, 0]].contiguous(), pos[idx[:, 1]].contiguous(), pos[idx[:, 2]].contiguous()
+        meta = hs.grid()[0]
+        e = (meta["aabb_max"] - meta["aabb_min"]).astype(np.float64)
+        diag = float(np.sqrt((e * e).sum()))
+        torch.cuda.synchronize()
+        entry = {"triangles": int(t.shape[0]), "box_diagonal": diag}
+
+        def leg(r, tmin=None, tmax=None):
+            tmm = None
+            if tmin is not None:
+                tmm = torch.empty((r.shape[0], 2), dtype=torch.float32, device=r.device)
+                tmm[:, 0], tmm[:, 1] = tmin, tmax
+            c = gs.crossings(r, tmm)
+            occ = gs.occluded(r, tmm) != 0
+            same_sorted = bool(torch.equal(gs.crossings(r, tmm, sort=True).raw, c.raw))
+            sub = r[:TORCH_RAYS].contiguous()
+            lo, hi = (float("-inf"), float("inf")) if tmin is None else (tmin, tmax)
+            bc, bf = torch_brute_crossings(sub, lo, hi, v0, v1, v2)
+            m = sub.shape[0]
+            out = measure({"crossings": lambda: gs.crossings(r, tmm, stream=st),
+                           "occluded": lambda: gs.occluded(r, tmm, stream=st),
+                           "torch_brute_force": lambda: torch_brute_crossings(sub, lo, hi, v0, v1, v2)}, r.shape[0],
+                          args.steps, args.warmup, per_arm={"torch_brute_force": (1, 1, m)})
+            for k in out:
+                out[k]["unit"] = "rays/s"
+            a, b = out["crossings"], out["occluded"]
+            return {"rays": int(r.shape[0]), "counted_rays": int((c.raw[:, 0] > 0).sum()), "occluded": int(occ.sum()),
+                    "crossings_total": int(c.raw[:, 0].sum(dtype=torch.int64)), "front_total": int(c.raw[:, 1].sum(dtype=torch.int64)),
+                    "max_count": int(c.raw[:, 0].max()), "tmin": tmin,
+                    "tmax": None if tmax is None else (tmax if np.isfinite(tmax) else "inf"),
+                    "implies": bool((occ | (c.raw[:, 0] == 0)).all()), "sorted_same_bytes": same_sorted,
+                    "torch_rays_with_another_count": int((bc != c.raw[:m, 0]).sum()),
+                    "torch_rays_with_another_front": int((bf != c.raw[:m, 1]).sum()), **out,
+                    "ratio_over_occluded": round(a["ms"] / b["ms"], 3), "larger_spread": max(a["spread"], b["spread"]),
+                    "speedup_over_torch": round(a["per_s"] / out["torch_brute_force"]["per_s"], 3)}
+
+        perm = torch.from_numpy(np.random.Generator(np.random.PCG64(41)).permutation(n)).cuda()
+        entry["shuffled"] = leg(rays[perm].contiguous())
+        tri_n = torch.from_numpy(np.ascontiguousarray(t[:, 3:6]).view(np.float32).copy()).cuda()
+        ao = ao_rays(rays, gs.trace_rays(rays).hits, tri_n, float((meta["aabb_max"] - meta["aabb_min"]).max()))
+        entry["ao_bounce"] = leg(ao, 1e-4 * diag, float("inf"))
+        del ao, rays
+        # inside / signed distance: distance_legs' jittered hit points
+        r1 = gs.primary_rays(gs.frame(W, H, 1))
+        h1 = gs.trace_rays(r1)
+        hit = h1.hits[:, 0] != -1
+        g = torch.Generator(device="cuda")
+        g.manual_seed(47)
+        p = r1[hit, :3] + r1[hit, 3:] * h1.t[hit][:, None]
+        p = (p + torch.randn(p.shape, generator=g, device="cuda") * (0.01 * float((pos.max(0).values - pos.min(0).values).norm()))).contiguous()
+        ins = gs.inside(p)
+        sd, pd = gs.signed_distance(p), gs.distance(p)
+        out = measure({"distance": lambda: gs.distance(p, stream=st), "inside": lambda: gs.inside(p, stream=st),
+                       "signed_distance": lambda: gs.signed_distance(p, stream=st)}, p.shape[0], args.steps, args.warmup)
+        for k in out:
+            out[k]["unit"] = "points/s"
+        entry["points"] = {"points": int(p.shape[0]), "inside_points": int(ins.sum()),
+                           "inside_parity_differs": int((gs.inside(p, rule="parity") != ins).sum()),
+                           "abs_signed_same_bits": bool(torch.equal(sd.dist.abs().view(torch.int32), pd.dist.view(torch.int32))),
+                           **out, "signed_over_distance": round(out["signed_distance"]["ms"] / out["distance"]["ms"], 3)}
+        res["scenes"][str(sid)] = entry
+        print(json.dumps({str(sid): entry}), flush=True)
+        gs.close()
+        hs.close()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print("wrote", args.out)
+
+
 def march_loop(gs, rays, max_steps, min_dist, st, sort=False):
     """What a caller had before rt_march_rays_device: the contract's loop as GpuScene.distance calls with torch float32
     arithmetic between them (one torch operation per rounding: the same bytes), on the rays still marching, until
@@ -603,12 +723,14 @@ def main():
     ap.add_argument("--occlusion", action="store_true", help="the occlusion legs (occlusion_legs) instead of the ray legs")
     ap.add_argument("--ao", action="store_true", help="the AO-frame legs (ao_legs) instead of the ray legs")
     ap.add_argument("--distance", action="store_true", help="the distance-query legs (distance_legs) instead of the ray legs")
+    ap.add_argument("--crossings", action="store_true", help="the crossing-query legs (crossing_legs) instead of the ray legs")
     ap.add_argument("--march", action="store_true", help="the march-query legs (march_legs) instead of the ray legs; "
                                                         "--steps / --warmup default to 1 there: a launch is long")
     ap.add_argument("--march-frame", action="store_true", help="the RT_ISECT_RAY_MARCH frame leg alone, this build beside "
                                                               "--parent-lib (march_frame_legs); --out is required")
     ap.add_argument("--out", default=None, help="default: profiles/rays_bench.json (--occlusion: profiles/occlusion_bench.json; "
-                                                "--ao: profiles/ao_bench.json; --distance: profiles/distance_bench.json; --march: profiles/march_bench.json)")
+                                                "--ao: profiles/ao_bench.json; --distance: profiles/distance_bench.json; --march: profiles/march_bench.json; "
+                                                "--crossings: profiles/crossings_bench.json)")
     args = ap.parse_args()
     if args.march_frame and args.out is None:
         raise SystemExit("--march-frame needs --out")
@@ -616,7 +738,7 @@ def main():
         args.steps = 1 if args.steps == ap.get_default("steps") else args.steps
         args.warmup = 1 if args.warmup == ap.get_default("warmup") else args.warmup
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "march_bench.json" if args.march else "ao_bench.json" if args.ao else "distance_bench.json" if args.distance else
+        args.out = os.path.join(ROOT, "profiles", "crossings_bench.json" if args.crossings else "march_bench.json" if args.march else "ao_bench.json" if args.ao else "distance_bench.json" if args.distance else
                                 "occlusion_bench.json" if args.occlusion else "rays_bench.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_rays.py measures on the GPU; none is visible")
@@ -624,6 +746,8 @@ def main():
         return march_frame_legs(args)
     if args.march:
         return march_legs(args)
+    if args.crossings:
+        return crossing_legs(args)
     if args.distance:
         return distance_legs(args)
     if args.ao:
