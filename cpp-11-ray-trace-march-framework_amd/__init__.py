@@ -839,79 +839,91 @@ class GpuScene:
         sort=True (RT_RAYS_SORT) traces the rays ordered by direction octant and entry cell -- for rays in no
         useful order; the results are the same bits, in input order."""
         import torch
-        host = isinstance(rays, np.ndarray)
-        if host:
-            if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != RAY_WORDS or not rays.flags["C_CONTIGUOUS"]:
-                raise ValueError("rays: a C-contiguous float32 array of shape [n, 6]")
-            d_rays = torch.from_numpy(rays).to(f"cuda:{self.device}")
-        elif isinstance(rays, torch.Tensor):
-            if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != RAY_WORDS:
-                raise ValueError("rays: a float32 tensor of shape [n, 6]")
-            if not rays.is_cuda or rays.device.index != self.device:
-                raise ValueError(f"rays: a tensor on cuda:{self.device} (host memory is not traced in place)")
-            if not rays.is_contiguous():
-                raise ValueError("rays: a contiguous tensor (a strided view would be read as other rays)")
-            d_rays = rays
-        else:
-            raise ValueError("rays: a torch CUDA tensor or a numpy array")
-        n = d_rays.shape[0]
-        dev = d_rays.device
-        hits = torch.empty((n, RAY_HIT_WORDS), dtype=torch.int32, device=dev)
-        rec = torch.empty((n, SAMPLE_REC_WORDS), dtype=torch.int32, device=dev) if count else None
+        self._array(rays, "rays", RAY_WORDS, "traced")
         flags = (RT_RAYS_COUNT if count else 0) | (RT_RAYS_SORT if sort else 0)
+        host, n, (hits, rec) = self._query("rt_trace_rays_device", [rays],
+                                           [((RAY_HIT_WORDS,), torch.int32), ((SAMPLE_REC_WORDS,), torch.int32) if count else None],
+                                           lambda n, i, o: (i[0], n, flags, o[0], o[1]), stream)
+        if host:
+            h = hits.view(RAY_HIT_DTYPE).reshape(n)
+            r = rec.view(SAMPLE_REC_DTYPE).reshape(n) if count else None
+            return RayHits(h["tri"], h["t"], h["u"], h["v"], h, r)
+        return RayHits(self._u32(hits[:, 0]), hits[:, 1].view(torch.float32), hits[:, 2].view(torch.float32),
+                       hits[:, 3].view(torch.float32), hits, rec)
+
+    def _array(self, a, name, words, verb):
+        """The one input check of the queries: `a` is a [n, words] float32 array of this name -- a C-contiguous numpy
+        array, or a contiguous torch tensor on the scene's device (which the query has `verb` in place).  Raises
+        ValueError otherwise; touches no device."""
+        import torch
+        if isinstance(a, np.ndarray):
+            if a.dtype != np.float32 or a.ndim != 2 or a.shape[1] != words or not a.flags["C_CONTIGUOUS"]:
+                raise ValueError(f"{name}: a C-contiguous float32 array of shape [n, {words}]")
+        elif isinstance(a, torch.Tensor):
+            if a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != words:
+                raise ValueError(f"{name}: a float32 tensor of shape [n, {words}]")
+            if not a.is_cuda or a.device.index != self.device:
+                raise ValueError(f"{name}: a tensor on cuda:{self.device} (host memory is not {verb} in place)")
+            if not a.is_contiguous():
+                raise ValueError(f"{name}: a contiguous tensor (a strided view would be read as other {name})")
+        else:
+            raise ValueError(f"{name}: a torch CUDA tensor or a numpy array")
+
+    def _to_device(self, a):
+        """A checked input (_array) on the scene's device: a numpy array is uploaded, a tensor is itself."""
+        import torch
+        return torch.from_numpy(a).to(f"cuda:{self.device}") if isinstance(a, np.ndarray) else a
+
+    def _query(self, fname, inputs, outputs, args, stream):
+        """The one call path of the queries.  inputs: checked arrays of one kind (_array; None: absent), the first
+        with one row per element; outputs: (trailing shape, dtype) per output the library writes (None: absent).
+        Allocates the outputs on the inputs' device, calls library function `fname` with
+        (handle, *args(n, input pointers, output pointers), stream) -- asynchronously on `stream` for tensors --
+        and returns (host, n, outputs): for numpy input the outputs come back as numpy arrays (synchronous)."""
+        import torch
+        host = isinstance(inputs[0], np.ndarray)
+        d_in = [None if a is None else self._to_device(a) for a in inputs]
+        n, dev = d_in[0].shape[0], d_in[0].device
+        outs = [None if o is None else torch.empty((n,) + o[0], dtype=o[1], device=dev) for o in outputs]
         if stream is not None and int(stream) != torch.cuda.current_stream(dev).cuda_stream:
             # the outputs come from torch's allocator on torch's current stream but are written on `stream`:
             # tell the allocator, so a result dropped early is not handed out again while the kernel runs
             ext = torch.cuda.ExternalStream(int(stream), device=dev)
-            for o in (hits, rec):
+            for o in outs:
                 if o is not None:
                     o.record_stream(ext)
+        ptrs = [[ctypes.c_void_p(t.data_ptr() if t is not None else 0) for t in ts] for ts in (d_in, outs)]
         L = tracer_lib()
-        _check(L.rt_trace_rays_device(self._h, ctypes.c_void_p(d_rays.data_ptr()), n, flags,
-                                      ctypes.c_void_p(hits.data_ptr()), ctypes.c_void_p(rec.data_ptr() if count else 0),
-                                      ctypes.c_void_p(self._stream(torch, stream))), L, "rt_trace_rays_device")
+        _check(getattr(L, fname)(self._h, *args(n, *ptrs), ctypes.c_void_p(self._stream(torch, stream))), L, fname)
         if host:
             if stream is not None:
                 torch.cuda.synchronize(dev)            # the copies below run on torch's stream
-            h = hits.cpu().numpy().view(RAY_HIT_DTYPE).reshape(n)
-            r = rec.cpu().numpy().view(SAMPLE_REC_DTYPE).reshape(n) if count else None
-            return RayHits(h["tri"], h["t"], h["u"], h["v"], h, r)
+            outs = [None if o is None else o.cpu().numpy() for o in outs]
+        return host, n, outs
+
+    @staticmethod
+    def _u32(words):
+        """int32 words as torch.uint32 where torch has it."""
+        import torch
         u32 = getattr(torch, "uint32", None)
-        tri = hits[:, 0].view(u32) if u32 is not None else hits[:, 0]
-        return RayHits(tri, hits[:, 1].view(torch.float32), hits[:, 2].view(torch.float32),
-                       hits[:, 3].view(torch.float32), hits, rec)
+        return words.view(u32) if u32 is not None else words
 
     def _interval_rays(self, rays, tminmax):
-        """The argument checks occluded() and crossings() share: (host, n, device, d_rays, d_tminmax or None)."""
+        """The argument checks occluded() and crossings() share: rays, and tminmax (None, or [n, 2] of the rays' kind)."""
         import torch
-        host = isinstance(rays, np.ndarray)
-        if host:
-            if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != RAY_WORDS or not rays.flags["C_CONTIGUOUS"]:
-                raise ValueError("rays: a C-contiguous float32 array of shape [n, 6]")
-            n = rays.shape[0]
-            if tminmax is not None and (not isinstance(tminmax, np.ndarray) or tminmax.dtype != np.float32 or
-                                        tminmax.shape != (n, 2) or not tminmax.flags["C_CONTIGUOUS"]):
+        self._array(rays, "rays", RAY_WORDS, "traced")
+        if tminmax is None:
+            return
+        n = rays.shape[0]
+        if isinstance(rays, np.ndarray):
+            if (not isinstance(tminmax, np.ndarray) or tminmax.dtype != np.float32 or tminmax.shape != (n, 2) or
+                    not tminmax.flags["C_CONTIGUOUS"]):
                 raise ValueError("tminmax: a C-contiguous float32 array of shape [n, 2], as the rays")
-            dev = torch.device(f"cuda:{self.device}")
-            d_rays = torch.from_numpy(rays).to(dev)
-            d_tmm = torch.from_numpy(tminmax).to(dev) if tminmax is not None else None
-        elif isinstance(rays, torch.Tensor):
-            if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != RAY_WORDS:
-                raise ValueError("rays: a float32 tensor of shape [n, 6]")
-            if not rays.is_cuda or rays.device.index != self.device:
-                raise ValueError(f"rays: a tensor on cuda:{self.device} (host memory is not traced in place)")
-            if not rays.is_contiguous():
-                raise ValueError("rays: a contiguous tensor (a strided view would be read as other rays)")
-            n = rays.shape[0]
-            if tminmax is not None:
-                if not isinstance(tminmax, torch.Tensor) or tminmax.dtype != torch.float32 or tuple(tminmax.shape) != (n, 2):
-                    raise ValueError("tminmax: a float32 tensor of shape [n, 2], as the rays")
-                if tminmax.device != rays.device or not tminmax.is_contiguous():
-                    raise ValueError("tminmax: a contiguous tensor on the rays' device")
-            d_rays, d_tmm, dev = rays, tminmax, rays.device
         else:
-            raise ValueError("rays: a torch CUDA tensor or a numpy array")
-        return host, n, dev, d_rays, d_tmm
+            if not isinstance(tminmax, torch.Tensor) or tminmax.dtype != torch.float32 or tuple(tminmax.shape) != (n, 2):
+                raise ValueError("tminmax: a float32 tensor of shape [n, 2], as the rays")
+            if tminmax.device != rays.device or not tminmax.is_contiguous():
+                raise ValueError("tminmax: a contiguous tensor on the rays' device")
 
     def occluded(self, rays, tminmax=None, sort=False, stream=None):
         """rt_occluded_rays_device: is anything hit inside the open interval (tmin, tmax) of each ray?  The
@@ -924,20 +936,10 @@ class GpuScene:
         a numpy bool [n] (synchronous).  The two inputs are of one kind.  Anything else raises ValueError before
         any launch.  sort=True (RT_RAYS_SORT): the same bytes, the rays traced in sorted order."""
         import torch
-        host, n, dev, d_rays, d_tmm = self._interval_rays(rays, tminmax)
-        occ = torch.empty((n,), dtype=torch.uint8, device=dev)
-        if stream is not None and int(stream) != torch.cuda.current_stream(dev).cuda_stream:
-            occ.record_stream(torch.cuda.ExternalStream(int(stream), device=dev))     # (as trace_rays)
-        L = tracer_lib()
-        _check(L.rt_occluded_rays_device(self._h, ctypes.c_void_p(d_rays.data_ptr()),
-                                         ctypes.c_void_p(d_tmm.data_ptr() if d_tmm is not None and n else 0), n,
-                                         RT_RAYS_SORT if sort else 0, ctypes.c_void_p(occ.data_ptr()),
-                                         ctypes.c_void_p(self._stream(torch, stream))), L, "rt_occluded_rays_device")
-        if host:
-            if stream is not None:
-                torch.cuda.synchronize(dev)            # the copy below runs on torch's stream
-            return occ.cpu().numpy().astype(bool)
-        return occ
+        self._interval_rays(rays, tminmax)
+        host, n, (occ,) = self._query("rt_occluded_rays_device", [rays, tminmax], [((), torch.uint8)],
+                                      lambda n, i, o: (i[0], i[1], n, RT_RAYS_SORT if sort else 0, o[0]), stream)
+        return occ.astype(bool) if host else occ
 
     def crossings(self, rays, tminmax=None, sort=False, stream=None):
         """rt_crossing_rays_device: how many surfaces does each ray cross inside the open interval (tmin, tmax), and
@@ -951,23 +953,13 @@ class GpuScene:
         input (synchronous).  For a closed, consistently oriented mesh and a ray over (0, +inf), count - 2 front is 1
         from a point inside and 0 from outside, and count & 1 is the parity test."""
         import torch
-        host, n, dev, d_rays, d_tmm = self._interval_rays(rays, tminmax)
-        raw = torch.empty((n, RAY_CROSS_WORDS), dtype=torch.int32, device=dev)
-        if stream is not None and int(stream) != torch.cuda.current_stream(dev).cuda_stream:
-            raw.record_stream(torch.cuda.ExternalStream(int(stream), device=dev))     # (as trace_rays)
-        L = tracer_lib()
-        _check(L.rt_crossing_rays_device(self._h, ctypes.c_void_p(d_rays.data_ptr()),
-                                         ctypes.c_void_p(d_tmm.data_ptr() if d_tmm is not None and n else 0), n,
-                                         RT_RAYS_SORT if sort else 0, ctypes.c_void_p(raw.data_ptr()),
-                                         ctypes.c_void_p(self._stream(torch, stream))), L, "rt_crossing_rays_device")
+        self._interval_rays(rays, tminmax)
+        host, n, (raw,) = self._query("rt_crossing_rays_device", [rays, tminmax], [((RAY_CROSS_WORDS,), torch.int32)],
+                                      lambda n, i, o: (i[0], i[1], n, RT_RAYS_SORT if sort else 0, o[0]), stream)
         if host:
-            if stream is not None:
-                torch.cuda.synchronize(dev)            # the copy below runs on torch's stream
-            r = raw.cpu().numpy().view(RAY_CROSS_DTYPE).reshape(n)
+            r = raw.view(RAY_CROSS_DTYPE).reshape(n)
             return Crossings(r["count"], r["front"], r)
-        u32 = getattr(torch, "uint32", None)
-        count, front = (raw[:, 0].view(u32), raw[:, 1].view(u32)) if u32 is not None else (raw[:, 0], raw[:, 1])
-        return Crossings(count, front, raw)
+        return Crossings(self._u32(raw[:, 0]), self._u32(raw[:, 1]), raw)
 
     def inside(self, points, rule="winding", dirs=None, stream=None):
         """Point-in-mesh classification of points [n, 3] by crossings(): from every point one ray per direction over
@@ -994,7 +986,8 @@ class GpuScene:
                 d.shape[0] % 2 != 1 or not np.isfinite(d).all()):
             raise ValueError("dirs: a finite float32 array of shape [k, 3], k odd")
         host = isinstance(points, np.ndarray)
-        d_pts = self._points(points)
+        self._array(points, "points", POINT_WORDS, "read")
+        d_pts = self._to_device(points)
         n, k, dev = d_pts.shape[0], d.shape[0], d_pts.device
         if n * k >= 1 << 31:
             raise ValueError("points x directions: below 2^31 rays")
@@ -1023,26 +1016,6 @@ class GpuScene:
         with self._torch_stream(torch, pd.dist.device, stream):
             return PointDist(torch.where(ins, -pd.dist, pd.dist), pd.tri, pd.closest, pd.raw)
 
-    def _points(self, points):
-        """The argument checks distance() and inside() share: the points on the scene's device."""
-        import torch
-        if isinstance(points, np.ndarray):
-            if (points.dtype != np.float32 or points.ndim != 2 or points.shape[1] != POINT_WORDS or
-                    not points.flags["C_CONTIGUOUS"]):
-                raise ValueError("points: a C-contiguous float32 array of shape [n, 3]")
-            d_pts = torch.from_numpy(points).to(f"cuda:{self.device}")
-        elif isinstance(points, torch.Tensor):
-            if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != POINT_WORDS:
-                raise ValueError("points: a float32 tensor of shape [n, 3]")
-            if not points.is_cuda or points.device.index != self.device:
-                raise ValueError(f"points: a tensor on cuda:{self.device} (host memory is not read in place)")
-            if not points.is_contiguous():
-                raise ValueError("points: a contiguous tensor (a strided view would be read as other points)")
-            d_pts = points
-        else:
-            raise ValueError("points: a torch CUDA tensor or a numpy array")
-        return d_pts
-
     def distance(self, points, closest=False, exhaustive=False, sort=False, stream=None):
         """rt_distance_points_device: Renderer::DistanceBruteForce for caller-supplied points [n, 3] -- per point the
         minimum of DistancePointTri over every triangle, bit for bit, and the lowest mesh triangle index that
@@ -1059,31 +1032,15 @@ class GpuScene:
         evaluates every triangle for every point; sort=True (RT_DIST_SORT) takes the points in Morton order of
         their position -- for points in no useful order.  Both give the same bytes, in input order."""
         import torch
-        host = isinstance(points, np.ndarray)
-        d_pts = self._points(points)
-        n = d_pts.shape[0]
-        dev = d_pts.device
-        raw = torch.empty((n, POINT_DIST_WORDS), dtype=torch.int32, device=dev)
-        cl = torch.empty((n, 3), dtype=torch.float32, device=dev) if closest else None
+        self._array(points, "points", POINT_WORDS, "read")
         flags = (RT_DIST_EXHAUSTIVE if exhaustive else 0) | (RT_DIST_SORT if sort else 0)
-        if stream is not None and int(stream) != torch.cuda.current_stream(dev).cuda_stream:
-            ext = torch.cuda.ExternalStream(int(stream), device=dev)                  # (as trace_rays)
-            for o in (raw, cl):
-                if o is not None:
-                    o.record_stream(ext)
-        L = tracer_lib()
-        _check(L.rt_distance_points_device(self._h, ctypes.c_void_p(d_pts.data_ptr()), n, flags,
-                                           ctypes.c_void_p(raw.data_ptr()),
-                                           ctypes.c_void_p(cl.data_ptr() if closest and n else 0),
-                                           ctypes.c_void_p(self._stream(torch, stream))), L, "rt_distance_points_device")
+        host, n, (raw, cl) = self._query("rt_distance_points_device", [points],
+                                         [((POINT_DIST_WORDS,), torch.int32), ((3,), torch.float32) if closest else None],
+                                         lambda n, i, o: (i[0], n, flags, o[0], o[1]), stream)
         if host:
-            if stream is not None:
-                torch.cuda.synchronize(dev)            # the copies below run on torch's stream
-            r = raw.cpu().numpy().view(POINT_DIST_DTYPE).reshape(n)
-            return PointDist(r["dist"], r["tri"], cl.cpu().numpy() if closest else None, r)
-        u32 = getattr(torch, "uint32", None)
-        tri = raw[:, 1].view(u32) if u32 is not None else raw[:, 1]
-        return PointDist(raw[:, 0].view(torch.float32), tri, cl, raw)
+            r = raw.view(POINT_DIST_DTYPE).reshape(n)
+            return PointDist(r["dist"], r["tri"], cl, r)
+        return PointDist(raw[:, 0].view(torch.float32), self._u32(raw[:, 1]), cl, raw)
 
     def march(self, rays, max_steps=128, min_dist=1e-3, exhaustive=False, sort=False, stream=None):
         """rt_march_rays_device: Renderer::RayMarch over DistanceBruteForce for caller-supplied rays [n, 6] (origin,
@@ -1102,19 +1059,7 @@ class GpuScene:
         words.  exhaustive=True (RT_MARCH_EXHAUSTIVE) evaluates every triangle at every step and stops no miss early;
         sort=True (RT_MARCH_SORT) marches the rays in RT_RAYS_SORT's order.  Both give the same bytes, in input order."""
         import torch
-        host = isinstance(rays, np.ndarray)
-        if host:
-            if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != RAY_WORDS or not rays.flags["C_CONTIGUOUS"]:
-                raise ValueError("rays: a C-contiguous float32 array of shape [n, 6]")
-        elif isinstance(rays, torch.Tensor):
-            if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != RAY_WORDS:
-                raise ValueError("rays: a float32 tensor of shape [n, 6]")
-            if not rays.is_cuda or rays.device.index != self.device:
-                raise ValueError(f"rays: a tensor on cuda:{self.device} (host memory is not read in place)")
-            if not rays.is_contiguous():
-                raise ValueError("rays: a contiguous tensor (a strided view would be read as other rays)")
-        else:
-            raise ValueError("rays: a torch CUDA tensor or a numpy array")
+        self._array(rays, "rays", RAY_WORDS, "read")
         if isinstance(max_steps, bool) or not isinstance(max_steps, (int, np.integer)) or not 1 <= max_steps <= MARCH_MAX_STEPS:
             raise ValueError(f"max_steps: an integer in [1, {MARCH_MAX_STEPS}]")
         try:
@@ -1123,26 +1068,15 @@ class GpuScene:
             raise ValueError("min_dist: a number") from None
         if min_dist != min_dist:
             raise ValueError("min_dist: not NaN")
-        d_rays = torch.from_numpy(rays).to(f"cuda:{self.device}") if host else rays
-        n = d_rays.shape[0]
-        dev = d_rays.device
-        raw = torch.empty((n, MARCH_HIT_WORDS), dtype=torch.int32, device=dev)
         flags = (RT_MARCH_EXHAUSTIVE if exhaustive else 0) | (RT_MARCH_SORT if sort else 0)
-        if stream is not None and int(stream) != torch.cuda.current_stream(dev).cuda_stream:
-            raw.record_stream(torch.cuda.ExternalStream(int(stream), device=dev))      # (as trace_rays)
         mp = MarchParams(int(max_steps), min_dist)
-        L = tracer_lib()
-        _check(L.rt_march_rays_device(self._h, ctypes.c_void_p(d_rays.data_ptr()), n, ctypes.byref(mp), flags,
-                                      ctypes.c_void_p(raw.data_ptr()),
-                                      ctypes.c_void_p(self._stream(torch, stream))), L, "rt_march_rays_device")
+        host, n, (raw,) = self._query("rt_march_rays_device", [rays], [((MARCH_HIT_WORDS,), torch.int32)],
+                                      lambda n, i, o: (i[0], n, ctypes.byref(mp), flags, o[0]), stream)
         if host:
-            if stream is not None:
-                torch.cuda.synchronize(dev)            # the copy below runs on torch's stream
-            r = raw.cpu().numpy().view(MARCH_HIT_DTYPE).reshape(n)
+            r = raw.view(MARCH_HIT_DTYPE).reshape(n)
             return MarchHit(r["steps"] != 0, r["t"], r["dist"], r["tri"], r["steps"], r)
-        u32 = getattr(torch, "uint32", None)
-        tri, steps = (raw[:, 2].view(u32), raw[:, 3].view(u32)) if u32 is not None else (raw[:, 2], raw[:, 3])
-        return MarchHit(raw[:, 3] != 0, raw[:, 0].view(torch.float32), raw[:, 1].view(torch.float32), tri, steps, raw)
+        return MarchHit(raw[:, 3] != 0, raw[:, 0].view(torch.float32), raw[:, 1].view(torch.float32),
+                        self._u32(raw[:, 2]), self._u32(raw[:, 3]), raw)
 
     def render_ao(self, frame, num_dirs=4, tmin=0.0, tmax=float("inf"), dirs=None, rotate=True, out=None,
                   counts=False, stream=None):

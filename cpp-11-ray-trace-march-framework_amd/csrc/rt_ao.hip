@@ -40,19 +40,10 @@ __device__ __forceinline__ bool ao_ray(const KParams& P, float ox, float oy, flo
                                        float tmin, float tmax)
 {
     bool hit = false;
-    if (finite_f32(ox) && finite_f32(oy) && finite_f32(oz) && finite_f32(dx) && finite_f32(dy) && finite_f32(dz))
-    {
-        if constexpr ((VAR & kVarFastRcp) != 0)
-        {
-            const float dm = fmaxf(fmaxf(fabsf(dx), fabsf(dy)), fabsf(dz));
-            if (wave_all(dm <= kRcpMaxDir))
-                hit = occlusion_walk<VAR>(P, ox, oy, oz, dx, dy, dz, tmin, tmax);
-            else
-                hit = occlusion_walk<VAR & ~kVarFastRcp>(P, ox, oy, oz, dx, dy, dz, tmin, tmax);
-        }
-        else
-            hit = occlusion_walk<VAR>(P, ox, oy, oz, dx, dy, dz, tmin, tmax);
-    }
+    if (RT_FINITE_RAY(ox, oy, oz, dx, dy, dz))
+        hit = rcp_vote<VAR>(dx, dy, dz, [&](auto v) {
+            return occlusion_walk<decltype(v)::value>(P, ox, oy, oz, dx, dy, dz, tmin, tmax);
+        });
     return hit;
 }
 
@@ -81,19 +72,10 @@ __global__ void __launch_bounds__(kWG) k_render_ao(KAo G)
             float t = 0.0f, u = 0.0f, v = 0.0f;
             uint32_t tri = rtd::kNoTri;
             bool hit = false;
-            if (finite_f32(ox) && finite_f32(oy) && finite_f32(oz) && finite_f32(dx) && finite_f32(dy) && finite_f32(dz))
-            {
-                if constexpr ((VAR & kVarFastRcp) != 0)
-                {
-                    const float dm = fmaxf(fmaxf(fabsf(dx), fabsf(dy)), fabsf(dz));
-                    if (wave_all(dm <= kRcpMaxDir))
-                        hit = rays_walk<VAR>(P, ox, oy, oz, dx, dy, dz, t, u, v, tri);
-                    else
-                        hit = rays_walk<VAR & ~kVarFastRcp>(P, ox, oy, oz, dx, dy, dz, t, u, v, tri);
-                }
-                else
-                    hit = rays_walk<VAR>(P, ox, oy, oz, dx, dy, dz, t, u, v, tri);
-            }
+            if (RT_FINITE_RAY(ox, oy, oz, dx, dy, dz))
+                hit = rcp_vote<VAR>(dx, dy, dz, [&](auto w) {
+                    return rays_walk<decltype(w)::value>(P, ox, oy, oz, dx, dy, dz, t, u, v, tri);
+                });
             if (hit)
             {
                 // 4. g = e1 x e2 from the triangle's {v0, e1, e2} record, n = g / |g| turned against d, p = o + t d
@@ -185,14 +167,7 @@ __global__ void __launch_bounds__(kWG) k_render_ao(KAo G)
 
 ao_fn render_ao_kernel(int var)
 {
-    switch (var)
-    {
-    case kRaysBase | kVarFastRcp | kRaysBox: return k_render_ao<kRaysBase | kVarFastRcp | kRaysBox>;
-    case kRaysBase | kRaysBox: return k_render_ao<kRaysBase | kRaysBox>;
-    case kRaysBase | kVarFastRcp: return k_render_ao<kRaysBase | kVarFastRcp>;
-    case kRaysBase: return k_render_ao<kRaysBase>;
-    default: return nullptr;
-    }
+    return ray_variant<0>(var, [](auto v) -> ao_fn { return k_render_ao<decltype(v)::value>; });
 }
 
 } // namespace rtk

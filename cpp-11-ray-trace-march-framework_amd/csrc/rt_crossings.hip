@@ -24,37 +24,18 @@ __global__ void __launch_bounds__(kWG) k_cross_rays(KParams P, const float2 *ray
 {
     static_assert((VAR & kVarCross) != 0 && (VAR & kVarRays) != 0 && (VAR & kVarAnyHit) == 0,
                   "the counting walk of caller-supplied rays");
-    const uint32_t k = blockIdx.x * kWG + threadIdx.x;
-    if (k >= n) return;
-    const uint32_t i = order ? uint32_t(order[k] >> kKeyBits) : k;
-    if (i >= n) return;             // (never, for a permutation: no sort word may index past the arrays)
-    const float2 *rp = rays + size_t(i) * 3u;
-    const float2 a = rp[0], b = rp[1], c = rp[2];
-    const float ox = a.x, oy = a.y, oz = b.x, dx = b.y, dy = c.x, dz = c.y;
-    float tmin = -__builtin_inff(), tmax = __builtin_inff();
-    if (tminmax)
-    {
-        const float2 m = tminmax[i];
-        tmin = m.x;
-        tmax = m.y;
-    }
+    uint32_t i;
+    if (!ray_slot(order, n, i)) return;
+    float ox, oy, oz, dx, dy, dz, tmin, tmax;
+    load_ray(rays, i, ox, oy, oz, dx, dy, dz);
+    load_interval(tminmax, i, tmin, tmax);
     uint32_t count = 0u, front = 0u;
     // {0, 0} without a walk: a non-finite ray, a NaN bound, an empty interval (k_occluded_rays' one compare); a ray
     // that misses the grid box leaves the walk before its first cell
-    if (finite_f32(ox) && finite_f32(oy) && finite_f32(oz) && finite_f32(dx) && finite_f32(dy) && finite_f32(dz) &&
-        tmin < tmax)
-    {
-        if constexpr ((VAR & kVarFastRcp) != 0)
-        {
-            const float dm = fmaxf(fmaxf(fabsf(dx), fabsf(dy)), fabsf(dz));
-            if (wave_all(dm <= kRcpMaxDir))
-                crossing_walk<VAR>(P, ox, oy, oz, dx, dy, dz, tmin, tmax, count, front);
-            else
-                crossing_walk<VAR & ~kVarFastRcp>(P, ox, oy, oz, dx, dy, dz, tmin, tmax, count, front);
-        }
-        else
-            crossing_walk<VAR>(P, ox, oy, oz, dx, dy, dz, tmin, tmax, count, front);
-    }
+    if (RT_FINITE_RAY(ox, oy, oz, dx, dy, dz) && tmin < tmax)
+        rcp_vote<VAR>(dx, dy, dz, [&](auto v) {
+            crossing_walk<decltype(v)::value>(P, ox, oy, oz, dx, dy, dz, tmin, tmax, count, front);
+        });
     out[i] = make_uint2(count, front);
 }
 
@@ -62,14 +43,7 @@ __global__ void __launch_bounds__(kWG) k_cross_rays(KParams P, const float2 *ray
 
 cross_fn cross_rays_kernel(int var)
 {
-    switch (var)
-    {
-    case kVarCross | kRaysBase | kVarFastRcp | kRaysBox: return k_cross_rays<kVarCross | kRaysBase | kVarFastRcp | kRaysBox>;
-    case kVarCross | kRaysBase | kRaysBox: return k_cross_rays<kVarCross | kRaysBase | kRaysBox>;
-    case kVarCross | kRaysBase | kVarFastRcp: return k_cross_rays<kVarCross | kRaysBase | kVarFastRcp>;
-    case kVarCross | kRaysBase: return k_cross_rays<kVarCross | kRaysBase>;
-    default: return nullptr;
-    }
+    return ray_variant<kVarCross>(var, [](auto v) -> cross_fn { return k_cross_rays<decltype(v)::value>; });
 }
 
 } // namespace rtk

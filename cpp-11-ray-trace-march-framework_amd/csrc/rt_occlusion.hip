@@ -16,43 +16,24 @@
 namespace rtk {
 namespace {
 
-// rays, order: as k_trace_rays.  tminmax: (tmin, tmax) per ray, or null = (-inf, +inf).  occluded[i] = 1 / 0.
+// rays, order, tminmax: rt_ray_common.h (ray_slot, load_ray, load_interval).  occluded[i] = 1 / 0.
 template <int VAR>
 __global__ void __launch_bounds__(kWG) k_occluded_rays(KParams P, const float2 *rays, const float2 *tminmax,
                                                        const unsigned long long *order, uint32_t n, uint8_t *occluded)
 {
     static_assert((VAR & kVarAnyHit) != 0 && (VAR & kVarRays) != 0, "the any-hit walk of caller-supplied rays");
-    const uint32_t k = blockIdx.x * kWG + threadIdx.x;
-    if (k >= n) return;
-    const uint32_t i = order ? uint32_t(order[k] >> kKeyBits) : k;
-    if (i >= n) return;             // (never, for a permutation: no sort word may index past the arrays)
-    const float2 *rp = rays + size_t(i) * 3u;
-    const float2 a = rp[0], b = rp[1], c = rp[2];
-    const float ox = a.x, oy = a.y, oz = b.x, dx = b.y, dy = c.x, dz = c.y;
-    float tmin = -__builtin_inff(), tmax = __builtin_inff();
-    if (tminmax)
-    {
-        const float2 m = tminmax[i];
-        tmin = m.x;
-        tmax = m.y;
-    }
+    uint32_t i;
+    if (!ray_slot(order, n, i)) return;
+    float ox, oy, oz, dx, dy, dz, tmin, tmax;
+    load_ray(rays, i, ox, oy, oz, dx, dy, dz);
+    load_interval(tminmax, i, tmin, tmax);
     bool hit = false;
     // 0 without a walk: a non-finite ray (as rt_trace_rays_device), a NaN bound, an empty interval -- the one
     // compare tmin < tmax is false for all of the last two
-    if (finite_f32(ox) && finite_f32(oy) && finite_f32(oz) && finite_f32(dx) && finite_f32(dy) && finite_f32(dz) &&
-        tmin < tmax)
-    {
-        if constexpr ((VAR & kVarFastRcp) != 0)
-        {
-            const float dm = fmaxf(fmaxf(fabsf(dx), fabsf(dy)), fabsf(dz));
-            if (wave_all(dm <= kRcpMaxDir))
-                hit = occlusion_walk<VAR>(P, ox, oy, oz, dx, dy, dz, tmin, tmax);
-            else
-                hit = occlusion_walk<VAR & ~kVarFastRcp>(P, ox, oy, oz, dx, dy, dz, tmin, tmax);
-        }
-        else
-            hit = occlusion_walk<VAR>(P, ox, oy, oz, dx, dy, dz, tmin, tmax);
-    }
+    if (RT_FINITE_RAY(ox, oy, oz, dx, dy, dz) && tmin < tmax)
+        hit = rcp_vote<VAR>(dx, dy, dz, [&](auto v) {
+            return occlusion_walk<decltype(v)::value>(P, ox, oy, oz, dx, dy, dz, tmin, tmax);
+        });
     occluded[i] = hit ? uint8_t(1) : uint8_t(0);
 }
 
@@ -60,14 +41,7 @@ __global__ void __launch_bounds__(kWG) k_occluded_rays(KParams P, const float2 *
 
 occluded_fn occluded_rays_kernel(int var)
 {
-    switch (var)
-    {
-    case kVarAnyHit | kRaysBase | kVarFastRcp | kRaysBox: return k_occluded_rays<kVarAnyHit | kRaysBase | kVarFastRcp | kRaysBox>;
-    case kVarAnyHit | kRaysBase | kRaysBox: return k_occluded_rays<kVarAnyHit | kRaysBase | kRaysBox>;
-    case kVarAnyHit | kRaysBase | kVarFastRcp: return k_occluded_rays<kVarAnyHit | kRaysBase | kVarFastRcp>;
-    case kVarAnyHit | kRaysBase: return k_occluded_rays<kVarAnyHit | kRaysBase>;
-    default: return nullptr;
-    }
+    return ray_variant<kVarAnyHit>(var, [](auto v) -> occluded_fn { return k_occluded_rays<decltype(v)::value>; });
 }
 
 } // namespace rtk

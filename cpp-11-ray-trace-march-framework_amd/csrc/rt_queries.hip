@@ -36,44 +36,62 @@ void query_params(const rt_scene *s, KParams& P, const rt_frame *f = nullptr)
     P.gates = nullptr;
 }
 
-// RT_RAYS_SORT / RT_DIST_SORT, under the scene's mutex: the caller fills *keys with its sort words on st
-// (sorted_begin), the grid build's radix sort orders them by their low `bits` bits (sorted_finish), and *sorted is
-// the order the query kernel then reads its input through.  The scratch is the scene's and is the one piece of
-// state the queries have: sorted calls are serialised by the scene's mutex, and one on another stream than the
-// last waits for it (rays_ev).  It grows -- a free and an allocation, which wait for the device -- only when
-// n exceeds every earlier sorted n.  rays_sorted_done, after the kernel's launch, marks the scratch's last use.
-int sorted_begin(rt_scene *s, hipStream_t st, uint32_t n, unsigned long long **keys)
-{
-    if (!s->rays_ev) RT_HIP(hipEventCreateWithFlags(&s->rays_ev, s->ev_order_flags));
-    if (s->rays_ev_recorded && st != s->rays_stream) RT_HIP(hipStreamWaitEvent(st, s->rays_ev, 0));
-    return rt_internal_sort_reserve(&s->rays_sort, n, keys);
-}
+// One lane of a query per input element
+inline dim3 lane_grid(uint32_t n) { return dim3((n + kWG - 1) / kWG); }
 
-int sorted_finish(rt_scene *s, hipStream_t st, uint32_t n, uint32_t bits, unsigned long long **sorted)
+// The ray queries' sort words (RT_RAYS_SORT, RT_MARCH_SORT): k_ray_keys' on st, to be sorted by ray_key_bits() bits
+int fill_ray_keys(const rt_scene *s, const KParams& P, const float2 *rays, uint32_t n, hipStream_t st,
+                  unsigned long long *keys)
 {
-    return rt_internal_sort_run(s->rays_sort, st, n, bits, sorted);
-}
-
-// The ray queries' sorted order: sort words of k_ray_keys
-int rays_sorted_order(rt_scene *s, const KParams& P, const float2 *rays, uint32_t n, hipStream_t st,
-                      unsigned long long **sorted)
-{
-    unsigned long long *keys = nullptr;
-    if (int rc = sorted_begin(s, st, n, &keys)) return rc;
     // cells per axis beyond 512 drop their low bits from the key (9 bits an axis)
     uint32_t shift = 0;
     while ((std::max(std::max(s->dims[0], s->dims[1]), s->dims[2]) - 1u) >> shift >= 512u) shift++;
-    hipLaunchKernelGGL(ray_keys_kernel(), dim3((n + kWG - 1) / kWG), dim3(kWG), 0, st, P, rays, n, shift, keys);
+    hipLaunchKernelGGL(ray_keys_kernel(), lane_grid(n), dim3(kWG), 0, st, P, rays, n, shift, keys);
     RT_HIP(hipGetLastError());
-    return sorted_finish(s, st, n, ray_key_bits(), sorted);
+    return RT_OK;
 }
 
+// The sort scratch's last use: the event a later sorted call on another stream waits for
 int rays_sorted_done(rt_scene *s, hipStream_t st)
 {
     RT_HIP(hipEventRecord(s->rays_ev, st));
     s->rays_stream = st;
     s->rays_ev_recorded = true;
     return RT_OK;
+}
+
+// The launch of every query over n caller-supplied elements, after its entry point has checked its arguments, called
+// ensure_device and filled its parameters.  launch(order) launches the query kernel on st reading its input through
+// `order` (null: in input order).
+//
+// Unsorted: that launch and nothing else -- no lock, no event: the kernel reads only what rt_scene_create wrote, so it
+// is ordered against nothing but its own stream.
+//
+// Sorted (RT_RAYS_SORT / RT_DIST_SORT / RT_MARCH_SORT), under the scene's mutex: fill_keys(keys) launches the kernel
+// that writes the n sort words on st, the grid build's radix sort orders them by their low key_bits bits, and
+// launch(sorted) reads the input through them.  The scratch is the scene's and is the one piece of state the queries
+// have: sorted calls are serialised by the scene's mutex, and one on another stream than the last waits for it
+// (rays_ev).  It grows -- a free and an allocation, which wait for the device -- only when n exceeds every earlier
+// sorted n.  rays_sorted_done, after the kernel's launch, marks the scratch's last use.
+template <class Keys, class Launch>
+int launch_query(rt_scene *s, hipStream_t st, uint32_t n, bool sort, uint32_t key_bits, Keys fill_keys, Launch launch)
+{
+    if (!sort)
+    {
+        launch(static_cast<const unsigned long long *>(nullptr));
+        RT_HIP(hipGetLastError());
+        return RT_OK;
+    }
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (!s->rays_ev) RT_HIP(hipEventCreateWithFlags(&s->rays_ev, s->ev_order_flags));
+    if (s->rays_ev_recorded && st != s->rays_stream) RT_HIP(hipStreamWaitEvent(st, s->rays_ev, 0));
+    unsigned long long *keys = nullptr, *sorted = nullptr;
+    if (int rc = rt_internal_sort_reserve(&s->rays_sort, n, &keys)) return rc;
+    if (int rc = fill_keys(keys)) return rc;
+    if (int rc = rt_internal_sort_run(s->rays_sort, st, n, key_bits, &sorted)) return rc;
+    launch(static_cast<const unsigned long long *>(sorted));
+    RT_HIP(hipGetLastError());
+    return rays_sorted_done(s, st);
 }
 
 // The scene's distance arrays (rt_dist_tree.h) as rt_scene_create wrote them: what the distance and march kernels share
@@ -167,21 +185,11 @@ int rt_trace_rays_device(rt_scene *s, const rt_ray *d_rays, uint32_t n, uint32_t
     if (!fn) return fail(RT_E_INVALID, "kernel variant not built: " + std::to_string(var));
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const float2 *rays = reinterpret_cast<const float2 *>(d_rays);
-    const dim3 grid((n + kWG - 1) / kWG), wg(kWG);
-    if (!sort)
-    {
-        hipLaunchKernelGGL(fn, grid, wg, 0, st, P, rays, static_cast<const unsigned long long *>(nullptr), n, d_hits,
-                           d_recs);
-        RT_HIP(hipGetLastError());
-        return RT_OK;
-    }
-    // RT_RAYS_SORT: the same trace kernel reading its rays through the sorted words (rays_sorted_order)
-    std::lock_guard<std::mutex> lk(s->mtx);
-    unsigned long long *sorted = nullptr;
-    if (int rc = rays_sorted_order(s, P, rays, n, st, &sorted)) return rc;
-    hipLaunchKernelGGL(fn, grid, wg, 0, st, P, rays, static_cast<const unsigned long long *>(sorted), n, d_hits, d_recs);
-    RT_HIP(hipGetLastError());
-    return rays_sorted_done(s, st);
+    return launch_query(
+        s, st, n, sort, ray_key_bits(), [&](unsigned long long *keys) { return fill_ray_keys(s, P, rays, n, st, keys); },
+        [&](const unsigned long long *order) {
+            hipLaunchKernelGGL(fn, lane_grid(n), dim3(kWG), 0, st, P, rays, order, n, d_hits, d_recs);
+        });
 }
 
 // Ray i is occluded iff the any-hit walk over (tmin, tmax) finds a test that counts (include/rt_tracer.h).  The
@@ -209,20 +217,11 @@ int rt_occluded_rays_device(rt_scene *s, const rt_ray *d_rays, const float *d_tm
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const float2 *rays = reinterpret_cast<const float2 *>(d_rays);
     const float2 *tmm = reinterpret_cast<const float2 *>(d_tminmax);
-    const dim3 grid((n + kWG - 1) / kWG), wg(kWG);
-    if (!sort)
-    {
-        hipLaunchKernelGGL(fn, grid, wg, 0, st, P, rays, tmm, static_cast<const unsigned long long *>(nullptr), n,
-                           d_occluded);
-        RT_HIP(hipGetLastError());
-        return RT_OK;
-    }
-    std::lock_guard<std::mutex> lk(s->mtx);
-    unsigned long long *sorted = nullptr;
-    if (int rc = rays_sorted_order(s, P, rays, n, st, &sorted)) return rc;
-    hipLaunchKernelGGL(fn, grid, wg, 0, st, P, rays, tmm, static_cast<const unsigned long long *>(sorted), n, d_occluded);
-    RT_HIP(hipGetLastError());
-    return rays_sorted_done(s, st);
+    return launch_query(
+        s, st, n, sort, ray_key_bits(), [&](unsigned long long *keys) { return fill_ray_keys(s, P, rays, n, st, keys); },
+        [&](const unsigned long long *order) {
+            hipLaunchKernelGGL(fn, lane_grid(n), dim3(kWG), 0, st, P, rays, tmm, order, n, d_occluded);
+        });
 }
 
 // d_out[i] = what the counting walk over (tmin, tmax) leaves for ray i (include/rt_tracer.h; kernels:
@@ -250,19 +249,11 @@ int rt_crossing_rays_device(rt_scene *s, const rt_ray *d_rays, const float *d_tm
     const float2 *rays = reinterpret_cast<const float2 *>(d_rays);
     const float2 *tmm = reinterpret_cast<const float2 *>(d_tminmax);
     uint2 *out = reinterpret_cast<uint2 *>(d_out);
-    const dim3 grid((n + kWG - 1) / kWG), wg(kWG);
-    if (!sort)
-    {
-        hipLaunchKernelGGL(fn, grid, wg, 0, st, P, rays, tmm, static_cast<const unsigned long long *>(nullptr), n, out);
-        RT_HIP(hipGetLastError());
-        return RT_OK;
-    }
-    std::lock_guard<std::mutex> lk(s->mtx);
-    unsigned long long *sorted = nullptr;
-    if (int rc = rays_sorted_order(s, P, rays, n, st, &sorted)) return rc;
-    hipLaunchKernelGGL(fn, grid, wg, 0, st, P, rays, tmm, static_cast<const unsigned long long *>(sorted), n, out);
-    RT_HIP(hipGetLastError());
-    return rays_sorted_done(s, st);
+    return launch_query(
+        s, st, n, sort, ray_key_bits(), [&](unsigned long long *keys) { return fill_ray_keys(s, P, rays, n, st, keys); },
+        [&](const unsigned long long *order) {
+            hipLaunchKernelGGL(fn, lane_grid(n), dim3(kWG), 0, st, P, rays, tmm, order, n, out);
+        });
 }
 
 // DistanceBruteForce for caller-supplied points (include/rt_tracer.h; kernels: rt_distance.hip).  The argument rules,
@@ -292,24 +283,18 @@ int rt_distance_points_device(rt_scene *s, const float *d_points, uint32_t n, ui
     // 0.20 ms for 1.4 M points, profiles/distance_bench.json).  Same bytes either way.
     const dist_fn fn = distance_points_kernel((flags & RT_DIST_EXHAUSTIVE) != 0u || s->ndist_blk <= kDistSmallBlocks);
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const dim3 grid((n + kWG - 1) / kWG), wg(kWG);
-    if (!(flags & RT_DIST_SORT))
-    {
-        hipLaunchKernelGGL(fn, grid, wg, 0, st, D);
-        RT_HIP(hipGetLastError());
-        return RT_OK;
-    }
-    // RT_DIST_SORT: the same kernel reading its points through the sorted words (as rays_sorted_order)
-    std::lock_guard<std::mutex> lk(s->mtx);
-    unsigned long long *keys = nullptr, *sorted = nullptr;
-    if (int rc = sorted_begin(s, st, n, &keys)) return rc;
-    hipLaunchKernelGGL(point_keys_kernel(), grid, wg, 0, st, D, keys);
-    RT_HIP(hipGetLastError());
-    if (int rc = sorted_finish(s, st, n, 32u, &sorted)) return rc;
-    D.order = sorted;
-    hipLaunchKernelGGL(fn, grid, wg, 0, st, D);
-    RT_HIP(hipGetLastError());
-    return rays_sorted_done(s, st);
+    // RT_DIST_SORT: the same kernel reading its points through sort words of k_point_keys, all 32 key bits of them
+    return launch_query(
+        s, st, n, (flags & RT_DIST_SORT) != 0u, 32u,
+        [&](unsigned long long *keys) {
+            hipLaunchKernelGGL(point_keys_kernel(), lane_grid(n), dim3(kWG), 0, st, D, keys);
+            RT_HIP(hipGetLastError());
+            return int(RT_OK);
+        },
+        [&](const unsigned long long *order) {
+            D.order = order;
+            hipLaunchKernelGGL(fn, lane_grid(n), dim3(kWG), 0, st, D);
+        });
 }
 
 // Renderer::RayMarch for caller-supplied rays (include/rt_tracer.h; kernel: rt_march.hip).  The argument rules, the
@@ -339,22 +324,18 @@ int rt_march_rays_device(rt_scene *s, const rt_ray *d_rays, uint32_t n, const rt
     for (int a = 0; a < 3; a++) M.vmax[a] = s->vmax[a];
     const march_fn fn = march_rays_kernel((flags & RT_MARCH_EXHAUSTIVE) != 0u);
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    const dim3 grid((n + kWG - 1) / kWG), wg(kWG);
-    if (!(flags & RT_MARCH_SORT))
-    {
-        hipLaunchKernelGGL(fn, grid, wg, 0, st, M);
-        RT_HIP(hipGetLastError());
-        return RT_OK;
-    }
-    KParams P;
-    query_params(s, P);
-    std::lock_guard<std::mutex> lk(s->mtx);
-    unsigned long long *sorted = nullptr;
-    if (int rc = rays_sorted_order(s, P, M.rays, n, st, &sorted)) return rc;
-    M.d.order = sorted;
-    hipLaunchKernelGGL(fn, grid, wg, 0, st, M);
-    RT_HIP(hipGetLastError());
-    return rays_sorted_done(s, st);
+    // RT_MARCH_SORT: RT_RAYS_SORT's order, whose keys need the grid's parameters -- built on that path alone
+    return launch_query(
+        s, st, n, (flags & RT_MARCH_SORT) != 0u, ray_key_bits(),
+        [&](unsigned long long *keys) {
+            KParams P;
+            query_params(s, P);
+            return fill_ray_keys(s, P, M.rays, n, st, keys);
+        },
+        [&](const unsigned long long *order) {
+            M.d.order = order;
+            hipLaunchKernelGGL(fn, lane_grid(n), dim3(kWG), 0, st, M);
+        });
 }
 
 int rt_primary_rays_device(rt_scene *s, const rt_frame *f, rt_ray *d_rays, void *hip_stream)

@@ -18,7 +18,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "rt_ray_common.h"     // finite_f32, kRcpMaxDir, kKeyBits, kRaysBase / kRaysBox: shared with rt_occlusion.hip
+#include "rt_ray_common.h"
 
 namespace rtk {
 namespace {
@@ -41,40 +41,28 @@ __device__ __forceinline__ uint32_t spread3(uint32_t v)      // 9 bits -> every 
     return v;
 }
 
-// rays: rt_ray as three 8-byte words ({ox, oy} {oz, dx} {dy, dz}: the ABI asks for 8-byte alignment).
+// rays, order: rt_ray_common.h (ray_slot, load_ray).
 // COUNT: the counting walk of k_trace_records with its full record; else the fast arm (VAR).
-// order (RT_RAYS_SORT; else null): lane k of the launch traces ray order[k] >> kKeyBits and writes that ray's
-// outputs, so the results land in input order whatever the order they are traced in.
 template <int VAR, bool COUNT>
 __global__ void __launch_bounds__(kWG) k_trace_rays(KParams P, const float2 *rays, const unsigned long long *order,
                                                     uint32_t n, rt_ray_hit *hits, rt_sample_rec *recs)
 {
-    const uint32_t k = blockIdx.x * kWG + threadIdx.x;
-    if (k >= n) return;
-    const uint32_t i = order ? uint32_t(order[k] >> kKeyBits) : k;
-    if (i >= n) return;             // (never, for a permutation: no sort word may index past the arrays)
-    const float2 *rp = rays + size_t(i) * 3u;
-    const float2 a = rp[0], b = rp[1], c = rp[2];
-    const float ox = a.x, oy = a.y, oz = b.x, dx = b.y, dy = c.x, dz = c.y;
+    uint32_t i;
+    if (!ray_slot(order, n, i)) return;
+    float ox, oy, oz, dx, dy, dz;
+    load_ray(rays, i, ox, oy, oz, dx, dy, dz);
     float t = 0.0f, u = 0.0f, v = 0.0f;
     uint32_t tri = rtd::kNoTri, voxel = rtd::kNoTri, steps = 0, tests = 0;
     bool hit = false;
-    // a non-finite ray is a miss without a walk (include/rt_tracer.h)
-    if (finite_f32(ox) && finite_f32(oy) && finite_f32(oz) && finite_f32(dx) && finite_f32(dy) && finite_f32(dz))
+    if (RT_FINITE_RAY(ox, oy, oz, dx, dy, dz))
     {
         if constexpr (COUNT)
             hit = grid_intersect<true, RT_TRI_MOLLER_TRUMBORE, kVarWaveGate | kVarDistSkip>(P, ox, oy, oz, dx, dy, dz, t, u,
                                                                                            v, tri, voxel, steps, tests);
-        else if constexpr ((VAR & kVarFastRcp) != 0)
-        {
-            const float dm = fmaxf(fmaxf(fabsf(dx), fabsf(dy)), fabsf(dz));
-            if (wave_all(dm <= kRcpMaxDir))
-                hit = rays_walk<VAR>(P, ox, oy, oz, dx, dy, dz, t, u, v, tri);
-            else
-                hit = rays_walk<VAR & ~kVarFastRcp>(P, ox, oy, oz, dx, dy, dz, t, u, v, tri);
-        }
         else
-            hit = rays_walk<VAR>(P, ox, oy, oz, dx, dy, dz, t, u, v, tri);
+            hit = rcp_vote<VAR>(dx, dy, dz, [&](auto w) {
+                return rays_walk<decltype(w)::value>(P, ox, oy, oz, dx, dy, dz, t, u, v, tri);
+            });
     }
     if (hits)
     {
@@ -108,11 +96,10 @@ __global__ void __launch_bounds__(kWG) k_ray_keys(KParams P, const float2 *rays,
 {
     const uint32_t i = blockIdx.x * kWG + threadIdx.x;
     if (i >= n) return;
-    const float2 *rp = rays + size_t(i) * 3u;
-    const float2 a = rp[0], b = rp[1], c = rp[2];
-    const float ox = a.x, oy = a.y, oz = b.x, dx = b.y, dy = c.x, dz = c.y;
+    float ox, oy, oz, dx, dy, dz;
+    load_ray(rays, i, ox, oy, oz, dx, dy, dz);
     uint32_t key = kMissKey;
-    if (finite_f32(ox) && finite_f32(oy) && finite_f32(oz) && finite_f32(dx) && finite_f32(dy) && finite_f32(dz))
+    if (RT_FINITE_RAY(ox, oy, oz, dx, dy, dz))
     {
         float nct0, nct1, nct2, dt0, dt1, dt2;
         int rem0, rem1, rem2, cs0, cs1, cs2, cell;
@@ -149,14 +136,7 @@ __global__ void __launch_bounds__(kWG) k_primary_rays(KParams P, float2 *rays, u
 rays_fn trace_rays_kernel(int var, bool count)
 {
     if (count) return k_trace_rays<0, true>;
-    switch (var)
-    {
-    case kRaysBase | kVarFastRcp | kRaysBox: return k_trace_rays<kRaysBase | kVarFastRcp | kRaysBox, false>;
-    case kRaysBase | kRaysBox: return k_trace_rays<kRaysBase | kRaysBox, false>;
-    case kRaysBase | kVarFastRcp: return k_trace_rays<kRaysBase | kVarFastRcp, false>;
-    case kRaysBase: return k_trace_rays<kRaysBase, false>;
-    default: return nullptr;
-    }
+    return ray_variant<0>(var, [](auto v) -> rays_fn { return k_trace_rays<decltype(v)::value, false>; });
 }
 
 primary_fn primary_rays_kernel() { return k_primary_rays; }

@@ -1,0 +1,38 @@
+"""What the build-guard tests share (a plain helper module, like ray_sets.py): the device compile of one csrc file
+with the library's parity-critical flags, the compiler's resource remarks of its kernels as a table, and the library's
+last error message.  The assertions on the table -- names, counts, scratch, LDS, occupancy, register limits -- stay in
+the tests."""
+import ctypes
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+# csrc/Makefile's FLAGS, for the device side alone
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
+         "--cuda-device-only"]
+needs_hipcc = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
+
+_FIELDS = (r"TotalSGPRs: (\d+)", r" VGPRs: (\d+)", r"ScratchSize \[bytes/lane\]: (\d+)",
+           r"Occupancy \[waves/SIMD\]: (\d+)", r"LDS Size \[bytes/block\]: (\d+)")
+
+
+def resource_table(src, extra, also=()):
+    """{mangled kernel name: (sgprs, vgprs, scratch bytes / lane, waves / SIMD, LDS bytes / block)} of every kernel in
+    `src`, from -Rpass-analysis=kernel-resource-usage; `extra` says what else the compile makes (["-c", "-o", obj] or
+    ["-S", "-o", asm]); `also`: regexes of further remark lines, appended to each kernel's tuple in that order."""
+    out = subprocess.run([HIPCC] + FLAGS + list(extra) + [src, "-Rpass-analysis=kernel-resource-usage"], check=True,
+                         capture_output=True, text=True).stderr
+    names = re.findall(r"Function Name: (\S+)", out)
+    cols = [[int(x) for x in re.findall(f, out)] for f in _FIELDS + tuple(also)]
+    assert names and all(len(c) == len(names) for c in cols), (len(names), [len(c) for c in cols])
+    return dict(zip(names, zip(*cols)))
+
+
+def last_error(L):
+    buf = ctypes.create_string_buffer(512)
+    L.rt_last_error(buf, 512)
+    return buf.value.decode()

@@ -12,7 +12,6 @@
 import ctypes
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -22,14 +21,11 @@ import ao_ref as A
 import occlusion_ref as R
 import synth_scenes as S
 from conftest import PKG_DIR, ROOT, load_package
+from hip_remarks import FLAGS, HIPCC, last_error, needs_hipcc, resource_table
 
 rtm = load_package()
 META = S.meta()
 AO_SRC = os.path.join(PKG_DIR, "csrc", "rt_ao.hip")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
-         "--cuda-device-only"]
-needs_hipcc = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 FAKE = ctypes.c_void_p(1)            # a scene handle the rejected calls never dereference
 INF = np.float32(np.inf)
 ULP = np.finfo(np.float32).eps       # 2^-23: one ulp of a float in [1, 2)
@@ -41,12 +37,6 @@ ULP = np.finfo(np.float32).eps       # 2^-23: one ulp of a float in [1, 2)
 SYNTH_VIEWS = ("inside", "stack1500", "stack2100", "degenerate", "zero_normals", "negative_octant", "scale_1500",
                "away", "flat_inplane")
 SCENE_VIEWS = {"scene1": (96, 54, 4), "scene8": (96, 54, 4)}
-
-
-def last_error(L):
-    buf = ctypes.create_string_buffer(512)
-    L.rt_last_error(buf, 512)
-    return buf.value.decode()
 
 
 def genray(oracle, cam, fov, W, H, spp):
@@ -456,16 +446,8 @@ AO_KERNELS = {"k_render_aoILi8394766E": (94, 64, 8), "k_render_aoILi8392718E": (
 
 @needs_hipcc
 def test_ao_kernels_use_no_scratch_no_lds_and_keep_their_registers(tmp_path):
-    out = subprocess.run([HIPCC] + FLAGS + ["-c", "-o", str(tmp_path / "ao.o"), AO_SRC,
-                          "-Rpass-analysis=kernel-resource-usage"], check=True, capture_output=True, text=True).stderr
-    names = re.findall(r"Function Name: (\S+)", out)
-    sgprs = [int(x) for x in re.findall(r"TotalSGPRs: (\d+)", out)]
-    vgprs = [int(x) for x in re.findall(r" VGPRs: (\d+)", out)]
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out)]
-    occ = [int(x) for x in re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", out)]
-    lds = [int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", out)]
-    assert len(names) == len(sgprs) == len(vgprs) == len(scratch) == len(occ) == len(lds) == 4
-    table = dict(zip(names, zip(sgprs, vgprs, scratch, occ, lds)))
+    table = resource_table(AO_SRC, ["-c", "-o", str(tmp_path / "ao.o")])
+    assert len(table) == 4
     print(table)
     for key, want in AO_KERNELS.items():
         hit = [n for n in table if key in n]

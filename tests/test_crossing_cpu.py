@@ -28,7 +28,8 @@ import occlusion_ref as R
 import ray_sets as RS
 import synth_scenes as S
 from conftest import PKG_DIR, ROOT, load_package
-from test_occlusion_cpu import CONVERSE_CAP, FAKE, FLAGS, HIPCC, genray, last_error, needs_hipcc
+from hip_remarks import FLAGS, HIPCC, last_error, needs_hipcc, resource_table
+from test_occlusion_cpu import CONVERSE_CAP, FAKE, genray
 
 rtm = load_package()
 META = S.meta()
@@ -364,16 +365,7 @@ def test_crossing_kernels_use_no_scratch_no_lds_and_keep_8_waves(tmp_path):
     """The four k_cross_rays instantiations (k_trace_rays' fast-arm variants | kVarCross 33554432): scratch 0, LDS 0,
     8 waves / SIMD by the compiler's estimate and by the hardware's admission rule, at most 64 VGPRs -- what the
     occlusion kernels hold."""
-    out = subprocess.run([HIPCC] + FLAGS + ["-c", "-o", str(tmp_path / "cross.o"), SRC,
-                          "-Rpass-analysis=kernel-resource-usage"], check=True, capture_output=True, text=True).stderr
-    names = re.findall(r"Function Name: (\S+)", out)
-    sgprs = [int(x) for x in re.findall(r"TotalSGPRs: (\d+)", out)]
-    vgprs = [int(x) for x in re.findall(r" VGPRs: (\d+)", out)]
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out)]
-    occ = [int(x) for x in re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", out)]
-    lds = [int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", out)]
-    assert len(names) == len(sgprs) == len(vgprs) == len(scratch) == len(occ) == len(lds)
-    table = dict(zip(names, zip(sgprs, vgprs, scratch, occ, lds)))
+    table = resource_table(SRC, ["-c", "-o", str(tmp_path / "cross.o")])
     print(table)
     # kVarCross 33554432 | kVarRays 8388608 | kVarWaveGate 2 | kVarDistSkip 8 [| kVarFastRcp 2048] [| 4096 | 4]
     base = 33554432 | 8388608 | 2 | 8

@@ -19,21 +19,12 @@ import pytest
 import distance_ref as D
 import synth_scenes as S
 from conftest import PKG_DIR, ROOT, load_kat, load_package
+from hip_remarks import FLAGS, HIPCC, last_error, needs_hipcc, resource_table
 
 rtm = load_package()
 DIST_SRC = os.path.join(PKG_DIR, "csrc", "rt_distance.hip")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
-         "--cuda-device-only"]
-needs_hipcc = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 FAKE = ctypes.c_void_p(1)            # a scene handle the rejected calls never dereference
 FLT_MAX = D.FLT_MAX
-
-
-def last_error(L):
-    buf = ctypes.create_string_buffer(512)
-    L.rt_last_error(buf, 512)
-    return buf.value.decode()
 
 
 # ------------------------------------------------------------------ 1. the reduce rule and the tie rule
@@ -255,16 +246,8 @@ DIST_KERNELS = {"k_distance_pointsILb0E": (85, 50, 8), "k_distance_pointsILb1E":
 
 @needs_hipcc
 def test_distance_kernels_use_no_scratch_no_lds_and_keep_their_registers(tmp_path):
-    out = subprocess.run([HIPCC] + FLAGS + ["-c", "-o", str(tmp_path / "dist.o"), DIST_SRC,
-                          "-Rpass-analysis=kernel-resource-usage"], check=True, capture_output=True, text=True).stderr
-    names = re.findall(r"Function Name: (\S+)", out)
-    sgprs = [int(x) for x in re.findall(r"TotalSGPRs: (\d+)", out)]
-    vgprs = [int(x) for x in re.findall(r" VGPRs: (\d+)", out)]
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out)]
-    occ = [int(x) for x in re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", out)]
-    lds = [int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", out)]
-    assert len(names) == len(sgprs) == len(vgprs) == len(scratch) == len(occ) == len(lds) == 3
-    table = dict(zip(names, zip(sgprs, vgprs, scratch, occ, lds)))
+    table = resource_table(DIST_SRC, ["-c", "-o", str(tmp_path / "dist.o")])
+    assert len(table) == 3
     print(table)
     for key, want in DIST_KERNELS.items():
         hit = [n for n in table if key in n]

@@ -13,20 +13,16 @@
 import json
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
 from conftest import PKG_DIR, ROOT, load_package
+from hip_remarks import HIPCC, needs_hipcc, resource_table
 
 HEADER = os.path.join(PKG_DIR, "csrc", "rt_setup_div.h")
 SRC = os.path.join(PKG_DIR, "csrc", "rt_kernels.hip")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 ROCM_INC = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(HIPCC))), "include")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
-         "--cuda-device-only"]
-needs_hipcc = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 
 # tests/test_build_guard.py's kernels: its 8-wave group, and the group it holds to the hardware rule
 EIGHT_WAVES = ("k_render_lanesILi0ELi80398E", "k_render_lanesILi0ELi78350E", "k_render_lanesILi0ELi76298E",
@@ -64,16 +60,7 @@ def test_header_is_hashed_at_the_same_position():
 
 @needs_hipcc
 def test_guarded_kernels_keep_their_registers(tmp_path):
-    out = subprocess.run([HIPCC] + FLAGS + ["-c", "-o", str(tmp_path / "rt.o"), SRC,
-                          "-Rpass-analysis=kernel-resource-usage"], check=True, capture_output=True,
-                         text=True).stderr
-    names = re.findall(r"Function Name: (\S+)", out)
-    sgprs = [int(x) for x in re.findall(r"SGPRs: (\d+)", out)]
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out)]
-    vgprs = [int(x) for x in re.findall(r"VGPRs: (\d+)", out)]
-    occ = [int(x) for x in re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", out)]
-    assert len(names) == len(sgprs) == len(scratch) == len(vgprs) == len(occ) and names
-    table = {n: (sg, sc, vg, oc) for n, sg, sc, vg, oc in zip(names, sgprs, scratch, vgprs, occ)}
+    table = {n: (sg, sc, vg, oc) for n, (sg, vg, sc, oc, ld) in resource_table(SRC, ["-c", "-o", str(tmp_path / "rt.o")]).items()}
     for key in EIGHT_WAVES:
         arm = {n: v for n, v in table.items() if key in n}
         assert arm, key

@@ -9,7 +9,6 @@
 import ctypes
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -19,21 +18,12 @@ import camera_matrices as C
 import march_ref as M
 import synth_scenes as S
 from conftest import ALT_REC_DTYPE, PKG_DIR, ROOT, load_package, read_gz
+from hip_remarks import FLAGS, HIPCC, last_error, needs_hipcc, resource_table
 
 rtm = load_package()
 MARCH_SRC = os.path.join(PKG_DIR, "csrc", "rt_march.hip")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
-         "--cuda-device-only"]
-needs_hipcc = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 FAKE = ctypes.c_void_p(1)            # a scene handle the rejected calls never dereference
 F = np.float32
-
-
-def last_error(L):
-    buf = ctypes.create_string_buffer(512)
-    L.rt_last_error(buf, 512)
-    return buf.value.decode()
 
 
 # ------------------------------------------------------------------ 1. march_ref against the reference's RayMarch
@@ -222,18 +212,9 @@ MARCH_KERNELS = {"k_march_raysILb0E": (94, 57, 8), "k_march_raysILb1E": (47, 23,
 
 @needs_hipcc
 def test_march_kernels_use_no_scratch_no_lds_and_keep_their_registers(tmp_path):
-    out = subprocess.run([HIPCC] + FLAGS + ["-c", "-o", str(tmp_path / "march.o"), MARCH_SRC,
-                          "-Rpass-analysis=kernel-resource-usage"], check=True, capture_output=True, text=True).stderr
-    names = re.findall(r"Function Name: (\S+)", out)
-    sgprs = [int(x) for x in re.findall(r"TotalSGPRs: (\d+)", out)]
-    vgprs = [int(x) for x in re.findall(r" VGPRs: (\d+)", out)]
-    agprs = [int(x) for x in re.findall(r" AGPRs: (\d+)", out)]
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out)]
-    occ = [int(x) for x in re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", out)]
-    lds = [int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", out)]
-    vspill = [int(x) for x in re.findall(r"VGPRs Spill: (\d+)", out)]
-    assert len(names) == len(sgprs) == len(vgprs) == len(agprs) == len(scratch) == len(occ) == len(lds) == len(vspill) == 2
-    table = dict(zip(names, zip(sgprs, vgprs, scratch, occ, lds, agprs, vspill)))
+    table = resource_table(MARCH_SRC, ["-c", "-o", str(tmp_path / "march.o")],
+                           also=(r" AGPRs: (\d+)", r"VGPRs Spill: (\d+)"))
+    assert len(table) == 2
     print(table)
     for key, want in MARCH_KERNELS.items():
         hit = [n for n in table if key in n]

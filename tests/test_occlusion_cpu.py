@@ -12,7 +12,6 @@
 import ctypes
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -21,26 +20,17 @@ import pytest
 import occlusion_ref as R
 import synth_scenes as S
 from conftest import PKG_DIR, ROOT, load_package
+from hip_remarks import FLAGS, HIPCC, last_error, needs_hipcc, resource_table
 
 rtm = load_package()
 META = S.meta()
 CASES = sorted(META["cases"])
 GEOM_COLS = ("hit", "tri", "voxel", "t", "u", "v", "steps", "tests")
 OCC_SRC = os.path.join(PKG_DIR, "csrc", "rt_occlusion.hip")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
-         "--cuda-device-only"]
-needs_hipcc = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 FAKE = ctypes.c_void_p(1)            # a scene handle the rejected calls never dereference
 # the header's cap on the converse of the implication: rays with ref.hit && ref.t < tmax that the occlusion walk
 # does not report, per view and interval, as a share of the view's hit rays
 CONVERSE_CAP = 0.01
-
-
-def last_error(L):
-    buf = ctypes.create_string_buffer(512)
-    L.rt_last_error(buf, 512)
-    return buf.value.decode()
 
 
 def frames_of(e):
@@ -231,16 +221,7 @@ def test_occlusion_device_ir_has_no_contraction_or_fast_math(tmp_path):
 def test_occlusion_kernels_use_no_scratch_no_lds_and_keep_8_waves(tmp_path):
     """The four k_occluded_rays instantiations (k_trace_rays' fast-arm variants | kVarAnyHit 16777216): scratch 0,
     LDS 0, 8 waves / SIMD by the compiler's estimate and by the hardware's admission rule, at most 64 VGPRs."""
-    out = subprocess.run([HIPCC] + FLAGS + ["-c", "-o", str(tmp_path / "occl.o"), OCC_SRC,
-                          "-Rpass-analysis=kernel-resource-usage"], check=True, capture_output=True, text=True).stderr
-    names = re.findall(r"Function Name: (\S+)", out)
-    sgprs = [int(x) for x in re.findall(r"TotalSGPRs: (\d+)", out)]
-    vgprs = [int(x) for x in re.findall(r" VGPRs: (\d+)", out)]
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out)]
-    occ = [int(x) for x in re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", out)]
-    lds = [int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", out)]
-    assert len(names) == len(sgprs) == len(vgprs) == len(scratch) == len(occ) == len(lds)
-    table = dict(zip(names, zip(sgprs, vgprs, scratch, occ, lds)))
+    table = resource_table(OCC_SRC, ["-c", "-o", str(tmp_path / "occl.o")])
     print(table)
     # kVarAnyHit 16777216 | kVarRays 8388608 | kVarWaveGate 2 | kVarDistSkip 8 [| kVarFastRcp 2048] [| 4096 | 4]
     for key in ("k_occluded_raysILi25171982E", "k_occluded_raysILi25169934E", "k_occluded_raysILi25167882E",

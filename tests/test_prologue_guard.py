@@ -9,18 +9,13 @@ floor(800 / (ceil(sgpr / 16) * 16 + 16)), as tests/test_build_guard.py checks it
 """
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
 from conftest import PKG_DIR
+from hip_remarks import HIPCC, resource_table
 
 SRC = os.path.join(PKG_DIR, "csrc", "rt_kernels.hip")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-# tests/test_build_guard.py's flags
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
-         "--cuda-device-only"]
 KERNELS = ("k_render_lanes_w64ILi0ELi80398E", "k_render_lanesILi0ELi80398E", "k_render_batch_w64ILi0ELi80398E")
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 
@@ -29,9 +24,8 @@ pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not ava
 def build(tmp_path_factory):
     """One compile for both tests: the assembly, and the resource remarks of the same code."""
     asm = tmp_path_factory.mktemp("prologue") / "rt_kernels.s"
-    remarks = subprocess.run([HIPCC] + FLAGS + ["-S", "-o", str(asm), SRC, "-Rpass-analysis=kernel-resource-usage"],
-                             check=True, capture_output=True, text=True).stderr
-    return asm.read_text().splitlines(), remarks
+    table = resource_table(SRC, ["-S", "-o", str(asm)])
+    return asm.read_text().splitlines(), table
 
 
 def kernel_body(lines, key):
@@ -53,14 +47,8 @@ def test_no_runtime_division_in_the_lane_kernels(build, key):
 
 
 def test_the_three_keep_eight_waves_by_the_hardware_rule(build):
-    out = build[1]
-    names = re.findall(r"Function Name: (\S+)", out)
-    sgprs = [int(x) for x in re.findall(r"SGPRs: (\d+)", out)]
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out)]
-    occ = [int(x) for x in re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", out)]
-    assert len(names) == len(sgprs) == len(scratch) == len(occ) and names
     for key in KERNELS:
-        arm = [(n, sg, sc, oc) for n, sg, sc, oc in zip(names, sgprs, scratch, occ) if key in n]
+        arm = [(n, sg, sc, oc) for n, (sg, vg, sc, oc, ld) in build[1].items() if key in n]
         assert len(arm) == 1, (key, arm)
         n, sg, sc, oc = arm[0]
         print(n, "sgpr", sg, "scratch", sc, "waves", oc)

@@ -15,20 +15,11 @@ import numpy as np
 import pytest
 
 from conftest import PKG_DIR, ROOT, load_package
+from hip_remarks import FLAGS, HIPCC, last_error, needs_hipcc, resource_table
 
 rtm = load_package()
 RAYS_SRC = os.path.join(PKG_DIR, "csrc", "rt_rays.hip")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
-         "--cuda-device-only"]
-needs_hipcc = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 FAKE = ctypes.c_void_p(1)            # a scene handle the rejected calls never dereference
-
-
-def last_error(L):
-    buf = ctypes.create_string_buffer(512)
-    L.rt_last_error(buf, 512)
-    return buf.value.decode()
 
 
 def test_symbols_structs_and_constants():
@@ -149,16 +140,7 @@ def test_rays_kernels_use_no_scratch_no_lds_and_keep_8_waves(tmp_path):
     RT_RAYS_SORT's k_ray_keys:
     scratch 0, LDS 0, and 8 waves / SIMD both by the compiler's estimate and by the hardware's admission rule
     800 // (ceil(sgpr / 16) * 16 + 16) -- the per-lane origin costs no wave."""
-    out = subprocess.run([HIPCC] + FLAGS + ["-c", "-o", str(tmp_path / "rays.o"), RAYS_SRC,
-                          "-Rpass-analysis=kernel-resource-usage"], check=True, capture_output=True, text=True).stderr
-    names = re.findall(r"Function Name: (\S+)", out)
-    sgprs = [int(x) for x in re.findall(r"TotalSGPRs: (\d+)", out)]
-    vgprs = [int(x) for x in re.findall(r" VGPRs: (\d+)", out)]
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out)]
-    occ = [int(x) for x in re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", out)]
-    lds = [int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", out)]
-    assert len(names) == len(sgprs) == len(vgprs) == len(scratch) == len(occ) == len(lds)
-    table = dict(zip(names, zip(sgprs, vgprs, scratch, occ, lds)))
+    table = resource_table(RAYS_SRC, ["-c", "-o", str(tmp_path / "rays.o")])
     print(table)
     rays = {n: v for n, v in table.items() if "k_trace_rays" in n}
     # kVarRays 8388608 | kVarWaveGate 2 | kVarDistSkip 8 [| kVarFastRcp 2048] [| kVarPackedRem 4096 | kVarSkipRun 4]
