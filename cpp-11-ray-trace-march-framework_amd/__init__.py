@@ -23,19 +23,20 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # Everything librt_tracer.so is compiled from: PMC counter files are valid only for this hash
-KERNEL_SOURCES = ("csrc/rt_kernels.hip", "csrc/rt_walk.h", "csrc/rt_kparams.h", "csrc/rt_plan.hip",
-                  "csrc/rt_scene.h", "csrc/rt_tracer.hip", "csrc/rt_grid_build.hip", "csrc/rt_device.h",
-                  "csrc/rt_internal.h", "csrc/rt_box_words.h", "csrc/rt_fref_slots.h", "csrc/rt_cam_bound.h", "csrc/rt_record_gate.h", "csrc/rt_setup_div.h", "csrc/rt_miss_mask.h", "csrc/rt_rays.hip",
-                  "csrc/rt_ray_common.h", "csrc/rt_occlusion.hip", "csrc/rt_crossings.hip", "csrc/rt_ao.hip", "csrc/rt_distance.hip",
-                  "csrc/rt_dist_tree.h", "csrc/rt_march.hip", "csrc/rt_dist_sweep.h", "csrc/rt_launch.hip", "csrc/rt_queries.hip", "csrc/rt_launch.h", "csrc/Makefile",
-                  "../include/rt_tracer.h")
+def kernel_sources():
+    """The rule of csrc/Makefile's HASHED, applied to the directory as it is now: every *.hip and *.h of csrc/ in
+    byte-sorted name order, then csrc/Makefile, then the ABI header (paths relative to the package)."""
+    import glob
+    csrc = glob.escape(os.path.join(HERE, "csrc"))
+    names = sorted(os.path.basename(p) for pat in ("*.hip", "*.h") for p in glob.glob(os.path.join(csrc, pat)))
+    return tuple("csrc/" + n for n in names) + ("csrc/Makefile", "../include/rt_tracer.h")
 
 
 def kernel_source_hash():
-    """SHA-256 (first 16 hex digits) over the kernel sources, in KERNEL_SOURCES order."""
+    """SHA-256 (first 16 hex digits) over kernel_sources(), in that order."""
     import hashlib
     h = hashlib.sha256()
-    for rel in KERNEL_SOURCES:
+    for rel in kernel_sources():
         with open(os.path.normpath(os.path.join(HERE, rel)), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]

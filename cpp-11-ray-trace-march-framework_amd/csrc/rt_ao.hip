@@ -14,6 +14,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "rt_item_coord.h"
 #include "rt_ray_common.h"
 
 namespace rtk {

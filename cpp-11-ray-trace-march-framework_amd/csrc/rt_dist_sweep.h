@@ -5,7 +5,7 @@
 //
 // The wave sweeps the box hierarchy top down, in index order.  A node is entered iff SOME active lane still needs
 // it: !(lb(node box) - margin > the lane's minimum), with margin = 1e-5 (|p|_inf + scene_scale), the ray march's
-// error model (rt_walk.h, ray_march).  A NaN bound never culls, and neither does a bound whose squares overflowed.
+// error model (rt_frame_isect.h, ray_march).  A NaN bound never culls, and neither does a bound whose squares overflowed.
 // Node boxes, triangle records and mesh indices of the sweep are read through wave-uniform addresses (scalar
 // loads); every active lane of the wave evaluates every triangle of an entered block.
 #pragma once

@@ -10,7 +10,7 @@
 //     (a binary search of the blocks' first codes, then a per-lane gather of the block's records);
 //   * the wave then sweeps the box hierarchy (rt_dist_tree.h) top down, in index order.  A node is entered iff
 //     SOME lane still needs it: !(lb(node box) - margin > the lane's minimum), with margin = 1e-5 (|p|_inf +
-//     scene_scale), the ray march's error model (rt_walk.h, ray_march).  A NaN bound never culls, and neither does a
+//     scene_scale), the ray march's error model (rt_frame_isect.h, ray_march).  A NaN bound never culls, and neither does a
 //     bound whose squares overflowed.  Node boxes, triangle records and mesh indices of the sweep are read through
 //     wave-uniform addresses (scalar loads); every lane of the wave evaluates every triangle of an entered block.
 //     (take, node_needed, eval_block, sweep and point_code: rt_dist_sweep.h, shared with rt_march.hip.)

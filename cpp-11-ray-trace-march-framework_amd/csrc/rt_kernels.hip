@@ -8,7 +8,7 @@
 // SAMPLE ORDER across lanes (renderer.cpp:87-122, hazard H10), averaged, gamma'd and packed
 // (renderer.cpp:124-133).
 //
-// The per-sample code lives in rt_walk.h; the heavy-first planner kernel in rt_plan.hip; the
+// The per-sample code lives in rt_item.h over rt_walk.h (the layers: DESIGN.md §4.38); the heavy-first planner kernel in rt_plan.hip; the
 // host side (scene tables, launches, the C ABI) in rt_tracer.hip.
 //
 // Scene layout in HBM (built once by rt_scene_create):
@@ -28,8 +28,9 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
 
-#include "rt_walk.h"
+#include "rt_item.h"
 
 namespace rtk {
 namespace {
@@ -413,22 +414,49 @@ __device__ __forceinline__ void prologue_args(const KParams& P)
                  "s"(P.m[7]), "s"(P.m[8]), "s"(P.org[0]), "s"(P.org[1]), "s"(P.org[2]));
 }
 
-// Wave `wib` (0-3) of launch block bid of nblk: its work item after the heavy-first / XCD-band map.
-template <int TRI, int VAR>
-__device__ __forceinline__ void lanes_block_wave(const KParams& P, uint32_t bid, uint32_t nblk, uint32_t wib,
-                                                 volatile uint32_t *t0v)
+// The first KParams of a lane kernel's argument -- the launch's heavy-first state, block map and wide-section marks
+// live there: the argument itself, or frame 0 of a multi-frame launch's KBatch.
+__device__ __forceinline__ const KParams& launch_params(const KParams& P) { return P; }
+__device__ __forceinline__ const KParams& launch_params(const KBatch& B) { return B.p[0]; }
+
+// Wave `wib` (0-3) of launch block bid of nblk lane blocks: its work item after the heavy-first / XCD-band map.
+// One body for both arguments.  A = KParams (k_render_lanes*): the item is the launch-wide item and
+// its KParams the kernel's own, as the entry loaded them.  A = KBatch (k_render_batch*): the launch's blocks are the
+// frames' blocks, frame-major; the item is counted from its frame's base, and its KParams are re-read from the kernarg
+// segment at the frame's offset.  The marks, the cost and the clock record go by the launch-wide item either way.
+template <int TRI, int VAR, class A>
+__device__ __forceinline__ void block_wave(const A& args, uint32_t bid, uint32_t nblk, uint32_t wib,
+                                           volatile uint32_t *t0v)
 {
+    constexpr bool BATCH = std::is_same<A, KBatch>::value;
+    constexpr uint32_t off0 = BATCH ? uint32_t(offsetof(KBatch, p)) : 0u;      // launch_params in the kernarg segment
+    const KParams& P0 = launch_params(args);
     uint32_t b;
     const uint32_t *mark;
-    if (!block_of_launch<VAR>(P, b, mark, bid, nblk)) return;
-    const uint32_t ver = P.hf_ver;
-    const uint32_t item = __builtin_amdgcn_readfirstlane(b * kWavesPerWG + wib);
+    if (!block_of_launch<VAR>(P0, b, mark, bid, nblk)) return;
+    const uint32_t ver = P0.hf_ver;
+    uint32_t gitem = b * kWavesPerWG + wib;                          // launch-wide item
+    if constexpr (!BATCH) gitem = __builtin_amdgcn_readfirstlane(gitem);
     if constexpr ((VAR & kVarWideHeavy) != 0)
-        if (P.wh_wgs && P.hf_ver && (P.wh_mark_in[item] & 0x7FFFFFFFu) == P.hf_ver) return;   // the wide section's
+        if (P0.wh_wgs && P0.hf_ver && (P0.wh_mark_in[gitem] & 0x7FFFFFFFu) == P0.hf_ver) return;   // the wide section's
+    uint32_t f = 0u, off = 0u, item = gitem;
+    if constexpr (BATCH)
+    {
+        f = batch_frame(args, b);
+        off = off0 + f * uint32_t(sizeof(KParams));
+        item = __builtin_amdgcn_readfirstlane(gitem - args.base[f] * kWavesPerWG);
+    }
+    // the item's KParams before the walk (a batch: a fresh read at each use, as late_params is)
+    auto item_params = [&]() -> const KParams& {
+        if constexpr (BATCH) return late_params(P0, off);
+        else return P0;
+    };
     if constexpr ((VAR & kVarWaveClock) != 0)
     {
-        // debug arm (RT_KERNEL_FLAG_WAVE_CLOCK): s_memtime at the item's start and end, and how
-        // many records the item tested in wave-uniform loops vs lane-loop iterations
+        // debug arm (RT_KERNEL_FLAG_WAVE_CLOCK, rt_debug_wave_clocks): s_memtime at the item's start and end, and
+        // how many records the item tested in wave-uniform loops vs lane-loop iterations.  A batch runs its
+        // heavy-first / wide-section machinery as in the product launch and stores, at the launch-wide item, the
+        // frame (bits 0-3) beside the records (bits 4-31), and the item's cost
         if ((threadIdx.x & 63u) == 0u)
         {
             wave_counters()[0] = 0u;
@@ -437,28 +465,38 @@ __device__ __forceinline__ void lanes_block_wave(const KParams& P, uint32_t bid,
         wave_lds_sync();
         const uint64_t r0 = __builtin_amdgcn_s_memrealtime();
         const uint64_t t0 = __builtin_amdgcn_s_memtime();
-        const ItemHead h = item_head<TRI, VAR>(P, item, mark);
+        const ItemHead h = item_head<TRI, VAR>(item_params(), item, mark);
         if (mark && h.mark_w == ver) return;                              // the front's
-        process_item<TRI, VAR>(P, item, 0u, h);
+        process_item<TRI, VAR>(item_params(), item, off, h);
         const uint64_t t1 = __builtin_amdgcn_s_memtime();
         const uint64_t r1 = __builtin_amdgcn_s_memrealtime();
         wave_lds_sync();
-        if ((threadIdx.x & 63u) == 0u)
-            store_wave_clock(P.wave_clk, item, t0, t1, r0, r1, wave_counters()[0], wave_counters()[1]);
+        if constexpr (BATCH)
+        {
+            const KParams& Q = late_params(P0, off0);
+            if ((threadIdx.x & 63u) == 0u)
+            {
+                store_wave_clock(Q.wave_clk, gitem, t0, t1, r0, r1, f | (min(wave_counters()[0], 0x0FFFFFFFu) << 4),
+                                 wave_counters()[1]);
+                if (Q.hf_measure) Q.hf_cost[gitem] = uint32_t(t1 - t0);
+            }
+        }
+        else if ((threadIdx.x & 63u) == 0u)
+            store_wave_clock(P0.wave_clk, gitem, t0, t1, r0, r1, wave_counters()[0], wave_counters()[1]);
     }
     else
     {
-        const bool hf = P.hf_measure != 0u;
+        const bool hf = P0.hf_measure != 0u;
         if (hf && (threadIdx.x & 63u) == 0u) t0v[threadIdx.x >> 6] = uint32_t(__builtin_amdgcn_s_memtime());
-        const ItemHead h = item_head<TRI, VAR>(P, item, mark);
+        const ItemHead h = item_head<TRI, VAR>(item_params(), item, mark);
         if (mark && h.mark_w == ver) return;                              // the front's: it stores the item's cost
-        process_item<TRI, VAR>(P, item, 0u, h);
-        const KParams& Q = late_params(P);
+        process_item<TRI, VAR>(item_params(), item, off, h);
+        const KParams& Q = late_params(P0, off0);
         if (Q.hf_measure)
         {
             const uint32_t t1 = uint32_t(__builtin_amdgcn_s_memtime());
             const uint32_t t0 = __builtin_amdgcn_readfirstlane(t0v[threadIdx.x >> 6]);
-            if ((threadIdx.x & 63u) == 0u) Q.hf_cost[__builtin_amdgcn_readfirstlane(item)] = t1 - t0;
+            if ((threadIdx.x & 63u) == 0u) Q.hf_cost[__builtin_amdgcn_readfirstlane(gitem)] = t1 - t0;
         }
     }
 }
@@ -471,7 +509,7 @@ __global__ void __launch_bounds__(kWG) k_render_lanes(KParams P)
     __shared__ uint32_t t0s[kWavesPerWG];
     volatile uint32_t *t0v = t0s;                 // a wave's start time waits in LDS across the walk
     prologue_args(P);
-    lanes_block_wave<TRI, VAR>(P, blockIdx.x, gridDim.x, threadIdx.x >> 6, t0v);
+    block_wave<TRI, VAR>(P, blockIdx.x, gridDim.x, threadIdx.x >> 6, t0v);
 }
 
 // The same launch blocks as one-wave workgroups (AUTO's whole-frame launches of >= wg64_min_blocks
@@ -496,7 +534,7 @@ __global__ void __launch_bounds__(64) k_render_lanes_w64(KParams P)
     // (vblocks straight from P: one of the entry's group of argument loads, not a round trip of its own)
     prologue_args(P);
     if (vbid >= P.vblocks) return;
-    lanes_block_wave<TRI, VAR>(P, vbid, P.vblocks, r & 3u, t0s);
+    block_wave<TRI, VAR>(P, vbid, P.vblocks, r & 3u, t0s);
 }
 
 // kVarWideHeavy: the wide section, launched on the scene's side stream beside the lane kernel
@@ -513,67 +551,6 @@ template <uint32_t G>
 __global__ void __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(7, 8))) k_render_wh_lds(KParams P)
 {
     wide_section_lds<false, G>(P, blockIdx.x);
-}
-
-// The multi-frame launch (KBatch): the launch's blocks are the frames' blocks, frame-major; the
-// heavy-first order (p[0]'s state) ranks them all, and every wave renders its item with its own
-// frame's parameters (KParams re-read from the kernarg segment at the frame's offset).
-// (The fused variant holds 83 SGPRs: 7 waves / SIMD.  Forced to 8 it spills a VGPR and measured
-// slower: rank of 4 / 8 0.256 / 0.139 ms vs 0.241 / 0.136, profiles/r03g_ab_wide_fused_*.json.)
-// Wave `wib` of launch block bid of nblk's lane blocks (after the fused wide section's workgroups).
-template <int TRI, int VAR>
-__device__ __forceinline__ void batch_block_wave(const KBatch& B, uint32_t bid, uint32_t nblk, uint32_t wib,
-                                                 volatile uint32_t *t0v)
-{
-    uint32_t b;
-    const uint32_t *mark;
-    if (!block_of_launch<VAR>(B.p[0], b, mark, bid, nblk)) return;
-    const uint32_t ver = B.p[0].hf_ver;
-    const uint32_t gitem = b * kWavesPerWG + wib;                    // launch-wide item
-    if constexpr ((VAR & kVarWideHeavy) != 0)
-        if (B.p[0].wh_wgs && B.p[0].hf_ver && (B.p[0].wh_mark_in[gitem] & 0x7FFFFFFFu) == B.p[0].hf_ver) return;
-    const uint32_t f = batch_frame(B, b);
-    const uint32_t off = uint32_t(offsetof(KBatch, p)) + f * uint32_t(sizeof(KParams));
-    const uint32_t item = __builtin_amdgcn_readfirstlane(gitem - B.base[f] * kWavesPerWG);
-    if constexpr ((VAR & kVarWaveClock) != 0)
-    {
-        // debug arm: the wave's clocks at its launch-wide item index (rt_debug_wave_clocks; the
-        // batch's heavy-first / wide-section machinery runs as in the product launch), with the
-        // frame (bits 0-3) and the records it tested in wave-uniform loops (bits 4-31), and its
-        // per-lane list iterations
-        if ((threadIdx.x & 63u) == 0u)
-        {
-            wave_counters()[0] = 0u;
-            wave_counters()[1] = 0u;
-        }
-        wave_lds_sync();
-        const uint64_t r0 = __builtin_amdgcn_s_memrealtime(), t0 = __builtin_amdgcn_s_memtime();
-        const ItemHead h = item_head<TRI, VAR>(late_params(B.p[0], off), item, mark);
-        if (mark && h.mark_w == ver) return;                              // the front's
-        process_item<TRI, VAR>(late_params(B.p[0], off), item, off, h);
-        const uint64_t t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-        wave_lds_sync();
-        const KParams& Q = late_params(B.p[0], uint32_t(offsetof(KBatch, p)));
-        if ((threadIdx.x & 63u) == 0u)
-        {
-            store_wave_clock(Q.wave_clk, gitem, t0, t1, r0, r1, f | (min(wave_counters()[0], 0x0FFFFFFFu) << 4),
-                             wave_counters()[1]);
-            if (Q.hf_measure) Q.hf_cost[gitem] = uint32_t(t1 - t0);
-        }
-        return;
-    }
-    const bool hf = B.p[0].hf_measure != 0u;
-    if (hf && (threadIdx.x & 63u) == 0u) t0v[threadIdx.x >> 6] = uint32_t(__builtin_amdgcn_s_memtime());
-    const ItemHead h = item_head<TRI, VAR>(late_params(B.p[0], off), item, mark);
-    if (mark && h.mark_w == ver) return;                                  // the front's: it stores the item's cost
-    process_item<TRI, VAR>(late_params(B.p[0], off), item, off, h);
-    const KParams& Q = late_params(B.p[0], uint32_t(offsetof(KBatch, p)));
-    if (Q.hf_measure)
-    {
-        const uint32_t t1 = uint32_t(__builtin_amdgcn_s_memtime());
-        const uint32_t t0 = __builtin_amdgcn_readfirstlane(t0v[threadIdx.x >> 6]);
-        if ((threadIdx.x & 63u) == 0u) Q.hf_cost[__builtin_amdgcn_readfirstlane(gitem)] = t1 - t0;
-    }
 }
 
 // The multi-frame launch (KBatch): the launch's blocks are the frames' blocks, frame-major; the
@@ -605,7 +582,7 @@ __device__ __forceinline__ void batch_body(const KBatch& B)
         nblk -= nw;
     }
     // (the lane blocks: one work item per wave, no split)
-    batch_block_wave<TRI, VAR & ~kVarLdsSplit>(B, bid, nblk, threadIdx.x >> 6, t0v);
+    block_wave<TRI, VAR & ~kVarLdsSplit>(B, bid, nblk, threadIdx.x >> 6, t0v);
 }
 
 template <int TRI, int VAR>
@@ -646,7 +623,7 @@ __device__ __forceinline__ void batch_w64_body(const KBatch& B)
     const uint32_t vbid = (r >> 2) * kXcds + w % kXcds;
     const uint32_t nv = B.p[0].vblocks;     // (one of the entry's group of argument loads)
     if (vbid >= nv) return;
-    batch_block_wave<TRI, VAR>(B, vbid, nv, r & 3u, t0s);
+    block_wave<TRI, VAR>(B, vbid, nv, r & 3u, t0s);
 }
 
 template <int TRI, int VAR>

@@ -9,7 +9,7 @@
 
 #include "rt_miss_mask.h"
 #include "rt_scene.h"
-#include "rt_walk.h"
+#include "rt_item_coord.h"
 
 namespace rtk {
 namespace {

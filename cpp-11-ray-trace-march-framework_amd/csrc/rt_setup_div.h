@@ -67,7 +67,7 @@ RT_SDIV_HD bool setup_div_operand_ok(float x)
 #if defined(__HIPCC__)
 // The wave's lanes whose x fails (W), for dda_setup's vote: the two compares of setup_div_operand_ok
 // as two ballots (a single compare's lane mask IS its ballot; a combined predicate would be
-// materialised in a VGPR and compared back, rt_walk.h wave_all).
+// materialised in a VGPR and compared back, rt_wave.h wave_all).
 __device__ __forceinline__ unsigned long long setup_div_bad_lanes(float x)
 {
     const float a = __builtin_fabsf(x);

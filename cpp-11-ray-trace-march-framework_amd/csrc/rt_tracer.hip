@@ -5,7 +5,7 @@
 //                   batched steps, records, hit IDs), the timing getters and the host copy-back paths
 //   rt_queries.hip  rt_trace_samples, the ray, occlusion and distance queries, primary rays, AO frames
 //   rt_launch.h     what the three share
-// The kernels: rt_kernels.hip (per-sample code in rt_walk.h), rt_rays.hip, rt_occlusion.hip, rt_ao.hip,
+// The kernels: rt_kernels.hip (per-sample code in rt_item.h over rt_walk.h), rt_rays.hip, rt_occlusion.hip, rt_ao.hip,
 // rt_distance.hip, rt_grid_build.hip; the heavy-first planner: rt_plan.hip; rt_kparams.h is what they share
 // with the host files.
 //

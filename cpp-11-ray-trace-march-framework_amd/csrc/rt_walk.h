@@ -1,7 +1,7 @@
-// rt_walk.h -- the per-sample device code of the render kernels (rt_kernels.hip only): the
-// reference's GenerateRay -> Grid::Intersect (3D-DDA over the packed cell words, box runs, the
-// per-camera-record ray/triangle tests) -> shading -> resolve path, one wave-sized work item at a
-// time (process_item), and the alternate intersectors.  See DESIGN.md §4.1-4.13.
+// rt_walk.h -- the grid walk, for every kernel that traces a ray: the reference's Grid::Intersect
+// (3D-DDA over the packed cell words, box runs, the per-camera-record ray/triangle tests) as
+// grid_intersect over dda_setup, test_cell and the DDA step macros.  See DESIGN.md §4.1-4.13; the
+// layers above it are rt_frame_isect.h, rt_item_coord.h and rt_item.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,48 +11,10 @@
 #include "rt_kparams.h"
 #include "rt_record_gate.h"
 #include "rt_setup_div.h"
+#include "rt_wave.h"
 
 namespace rtk {
 namespace {
-
-// Morton decode of an 8-bit index inside a 16x16 tile: x = even bits, y = odd bits.
-__device__ __forceinline__ uint32_t compact_bits(uint32_t v)
-{
-    v &= 0x55u;
-    v = (v | (v >> 1)) & 0x33u;
-    v = (v | (v >> 2)) & 0x0Fu;
-    return v;
-}
-
-// Orders this wave's LDS writes before its later LDS reads of other lanes' data (a wave
-// executes its LDS operations in order; this keeps the compiler from reordering them).
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-// Workgroup barrier for the LDS tier's reductions (kVarLdsSplit): this wave's LDS (and scalar)
-// operations complete, then s_barrier.  The memory clobber keeps the compiler from moving LDS accesses
-// across it (the s_barrier builtin alone is not a memory operation).
-__device__ __forceinline__ void lds_barrier()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-// kVarLdsSplit: the per-lane (t, list position) and (u, v) of every wave of the workgroup,
-// double-buffered by reduction parity: [parity][wave][lane] each
-__device__ __forceinline__ float2 *lds_red_tk()
-{
-    __shared__ float2 r[2 * kWavesPerWG * 64];
-    return r;
-}
-__device__ __forceinline__ float2 *lds_red_uv()
-{
-    __shared__ float2 r[2 * kWavesPerWG * 64];
-    return r;
-}
 
 // kVarLdsSplit: cell lists shorter than this (in every lane) are tested whole by every wave, with no
 // reduction; longer ones are split between the workgroup's waves
@@ -60,79 +22,6 @@ __device__ __forceinline__ float2 *lds_red_uv()
 #define RT_LDS_SPLIT_MIN 8
 #endif
 constexpr uint32_t kLdsSplitMin = RT_LDS_SPLIT_MIN;
-
-// kVarWaveClock debug counters of this wave: [0] records tested in wave-uniform loops,
-// [1] iterations of the per-lane list loop
-__device__ __forceinline__ uint32_t *wave_counters()
-{
-    __shared__ uint32_t c[kWavesPerWG * 2u];
-    return c + (threadIdx.x >> 6) * 2u;
-}
-
-// Wave-uniform "every active lane": the predicate's lane mask against exec.  Pass a single
-// compare: a predicate combined from several is materialised in a VGPR and compared back
-// (2 VALU per vote, seen in the empty-run loop's ISA), where a compare's mask is the ballot.
-__device__ __forceinline__ bool wave_all(bool p)
-{
-    return __builtin_amdgcn_ballot_w64(p) == __builtin_amdgcn_ballot_w64(true);
-}
-
-// v of lane (lane & ~3) + J: a DPP quad_perm broadcast within each quad of lanes (every lane of
-// the quad must be active, as in process_item's resolve, where the whole wave is)
-template <int J>
-__device__ __forceinline__ float quad_bcast(float v)
-{
-    constexpr int ctrl = J | (J << 2) | (J << 4) | (J << 6);
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xF, 0xF, false));
-}
-template <int J>
-__device__ __forceinline__ uint32_t quad_bcast_u(uint32_t v)
-{
-    constexpr int ctrl = J | (J << 2) | (J << 4) | (J << 6);
-    return uint32_t(__builtin_amdgcn_update_dpp(0, int(v), ctrl, 0xF, 0xF, false));
-}
-
-__device__ __forceinline__ bool first_active_lane()
-{
-    return (threadIdx.x & 63u) == uint32_t(__ffsll((long long)__ballot(1)) - 1);
-}
-
-// The kernel's KParams re-read from the kernarg segment.  Parameters used only after the
-// walk (output, shading, tile bookkeeping) are taken from here, so the compiler reloads them
-// with s_load after the walk instead of holding ~30 SGPRs of them live across it (the render
-// kernels' SGPR budget decides 8 vs 7 waves per SIMD).  The empty asm hides the pointer's
-// origin (a register round trip), so these loads cannot be merged with the kernel entry's.
-// off: byte offset of the frame's KParams in the kernarg segment (0 for the single-frame
-// kernels, whose first argument is the KParams; a frame of KBatch in the batch kernel).
-__device__ __forceinline__ const KParams& late_params(const KParams& P, uint32_t off = 0u)
-{
-    (void)P;
-    const uint64_t a = uint64_t(__builtin_amdgcn_kernarg_segment_ptr()) + off;
-    uint32_t lo = uint32_t(a), hi = uint32_t(a >> 32);
-    asm volatile("" : "+v"(lo), "+v"(hi));
-    lo = __builtin_amdgcn_readfirstlane(lo);
-    hi = __builtin_amdgcn_readfirstlane(hi);
-    return *(const KParams *)(const __attribute__((address_space(4))) KParams *)((uint64_t(hi) << 32) | lo);
-}
-
-// The batch kernels' KBatch, re-read from the kernarg segment (as late_params).
-__device__ __forceinline__ const KBatch& late_batch()
-{
-    const uint64_t a = uint64_t(__builtin_amdgcn_kernarg_segment_ptr());
-    uint32_t lo = uint32_t(a), hi = uint32_t(a >> 32);
-    asm volatile("" : "+v"(lo), "+v"(hi));
-    lo = __builtin_amdgcn_readfirstlane(lo);
-    hi = __builtin_amdgcn_readfirstlane(hi);
-    return *(const KBatch *)(const __attribute__((address_space(4))) KBatch *)((uint64_t(hi) << 32) | lo);
-}
-
-// Frame of launch block b (wave-uniform).
-__device__ __forceinline__ uint32_t batch_frame(const KBatch& B, uint32_t b)
-{
-    uint32_t f = 0;
-    for (uint32_t j = 1; j < kMaxBatch; j++) f += (j < B.nframes && b >= B.base[j]) ? 1u : 0u;
-    return f;
-}
 
 // CSR range of a cell: one u32 load of the packed (start << 11 | count) word when the scene
 // fits the packing (every scene of the reference does), else the two CSR offsets (a cell of
@@ -580,12 +469,16 @@ __device__ __forceinline__ bool test_cell(const KParams& P, float ox, float oy, 
 // updates run unconditionally -- when MORE is false the caller breaks and the state is dead --
 // so the step has no divergent branch.  Sets NCT_AX to the step axis' crossing t and MORE to
 // false when the ray leaves the grid (grid.cpp:275-276).
-#define RT_DDA_ADVANCE_ADD(NCT_AX, MORE)                                                       \
-    do {                                                                                       \
+// (RT_DDA_AXIS_: the step axis, written once for the four steps below; each expands it in place, so the tokens
+// the compiler sees are those of the written-out form)
+#define RT_DDA_AXIS_                                                                           \
         const float m_ = __builtin_fminf(__builtin_fminf(nct0, nct1), nct2);                   \
         const bool a2_ = nct2 == m_;                                                           \
         const bool a1_ = !a2_ && nct1 == m_;                                                   \
-        const bool a0_ = !a2_ && !a1_;                                                         \
+        const bool a0_ = !a2_ && !a1_
+#define RT_DDA_ADVANCE_ADD(NCT_AX, MORE)                                                       \
+    do {                                                                                       \
+        RT_DDA_AXIS_;                                                                          \
         NCT_AX = m_;                                                                           \
         MORE = (a2_ ? rem2 : (a1_ ? rem1 : rem0)) != 0;                                        \
         nct0 += a0_ ? dt0 : 0.0f;                                                              \
@@ -603,10 +496,7 @@ __device__ __forceinline__ bool test_cell(const KParams& P, float ox, float oy, 
 constexpr int kRemGuards = int((1u << 10) | (1u << 21) | (1u << 31));
 #define RT_DDA_ADVANCE_PACKED(NCT_AX, MORE)                                                    \
     do {                                                                                       \
-        const float m_ = __builtin_fminf(__builtin_fminf(nct0, nct1), nct2);                   \
-        const bool a2_ = nct2 == m_;                                                           \
-        const bool a1_ = !a2_ && nct1 == m_;                                                   \
-        const bool a0_ = !a2_ && !a1_;                                                         \
+        RT_DDA_AXIS_;                                                                          \
         NCT_AX = m_;                                                                           \
         remp -= a2_ ? (1 << 22) : (a1_ ? (1 << 11) : 1);                                       \
         MORE = (remp & kRemGuards) == 0;                                                       \
@@ -620,10 +510,7 @@ constexpr int kRemGuards = int((1u << 10) | (1u << 21) | (1u << 31));
 // empty-run blocks of grid_intersect read MORE from the packed word after the block).
 #define RT_DDA_BARE_STEP()                                                                     \
     do {                                                                                       \
-        const float m_ = __builtin_fminf(__builtin_fminf(nct0, nct1), nct2);                   \
-        const bool a2_ = nct2 == m_;                                                           \
-        const bool a1_ = !a2_ && nct1 == m_;                                                   \
-        const bool a0_ = !a2_ && !a1_;                                                         \
+        RT_DDA_AXIS_;                                                                          \
         remp -= a2_ ? (1 << 22) : (a1_ ? (1 << 11) : 1);                                       \
         nct0 += a0_ ? dt0 : 0.0f;                                                              \
         nct1 += a1_ ? dt1 : 0.0f;                                                              \
@@ -637,10 +524,7 @@ constexpr int kRemGuards = int((1u << 10) | (1u << 21) | (1u << 31));
 // that was 0 borrows into its guard bit when the step leaves the box.
 #define RT_DDA_ADVANCE_BOX(NCT_AX, MORE)                                                       \
     do {                                                                                       \
-        const float m_ = __builtin_fminf(__builtin_fminf(nct0, nct1), nct2);                   \
-        const bool a2_ = nct2 == m_;                                                           \
-        const bool a1_ = !a2_ && nct1 == m_;                                                   \
-        const bool a0_ = !a2_ && !a1_;                                                         \
+        RT_DDA_AXIS_;                                                                          \
         NCT_AX = m_;                                                                           \
         const int u_ = a2_ ? (1 << 22) : (a1_ ? (1 << 11) : 1);                                \
         remp -= u_;                                                                            \
@@ -653,28 +537,28 @@ constexpr int kRemGuards = int((1u << 10) | (1u << 21) | (1u << 31));
     } while (0)
 // A step inside a box run: only the crossing times and the box counts move; the run's end
 // rebuilds the cell index and the remaining-cell counts from the box counts' difference.
-#define RT_DDA_BOX_BARE_STEP()                                                                 \
-    do {                                                                                       \
+// (RT_DDA_BOX_AXIS_, RT_DDA_BOX_MOVE_: its axis choice and its move, written once for the two forms)
+#define RT_DDA_BOX_AXIS_                                                                       \
         const float m_ = __builtin_fminf(__builtin_fminf(nct0, nct1), nct2);                   \
         const bool a2_ = nct2 == m_;                                                           \
-        const bool e1_ = nct1 == m_;                                                           \
+        const bool e1_ = nct1 == m_
+#define RT_DDA_BOX_MOVE_                                                                       \
         boxw -= a2_ ? (1 << 22) : (e1_ ? (1 << 11) : 1);                                       \
         nct0 += (a2_ | e1_) ? 0.0f : dt0;                                                      \
         nct1 += (e1_ & !a2_) ? dt1 : 0.0f;                                                     \
-        nct2 += a2_ ? dt2 : 0.0f;                                                              \
+        nct2 += a2_ ? dt2 : 0.0f
+#define RT_DDA_BOX_BARE_STEP()                                                                 \
+    do {                                                                                       \
+        RT_DDA_BOX_AXIS_;                                                                      \
+        RT_DDA_BOX_MOVE_;                                                                      \
     } while (0)
 // RT_DDA_BOX_BARE_STEP that also hands out the crossing it takes (kVarAnyHit: the last one of a run is the
 // run's largest, which decides whether the walk has passed tmax).
 #define RT_DDA_BOX_BARE_STEP_T(NCT_AX)                                                         \
     do {                                                                                       \
-        const float m_ = __builtin_fminf(__builtin_fminf(nct0, nct1), nct2);                   \
-        const bool a2_ = nct2 == m_;                                                           \
-        const bool e1_ = nct1 == m_;                                                           \
+        RT_DDA_BOX_AXIS_;                                                                      \
         NCT_AX = m_;                                                                           \
-        boxw -= a2_ ? (1 << 22) : (e1_ ? (1 << 11) : 1);                                       \
-        nct0 += (a2_ | e1_) ? 0.0f : dt0;                                                      \
-        nct1 += (e1_ & !a2_) ? dt1 : 0.0f;                                                     \
-        nct2 += a2_ ? dt2 : 0.0f;                                                              \
+        RT_DDA_BOX_MOVE_;                                                                      \
     } while (0)
 constexpr int kBoxUnits3 = 3 | (3 << 11) | (3 << 22);   // 3 in every box-count field
 
@@ -824,61 +708,6 @@ __device__ __forceinline__ uint32_t exit_voxel(int remp, int cell, int cs0, int 
 {
     const uint32_t g = uint32_t(remp) & uint32_t(kRemGuards);
     return uint32_t(cell - ((g & (1u << 10)) ? cs0 : ((g & (1u << 21)) ? cs1 : cs2)));
-}
-
-// The cell whose CSR list holds reference k: off[c] <= k < off[c + 1] (records of a hit: the walk
-// accepts a hit only inside the cell being tested, grid.cpp:258-271, so this is that cell).
-__device__ __forceinline__ uint32_t cell_of_ref(const KParams& P, uint32_t k)
-{
-    uint32_t lo = 0u, hi = uint32_t(P.dim[0]) * uint32_t(P.dim[1]) * uint32_t(P.dim[2]);   // off[hi] = R > k
-    while (hi - lo > 1u)
-    {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (P.off[mid] <= k) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// The colour words of a record (the wide section stores them after its resolve).
-__device__ __forceinline__ void store_record_colour(const KParams& Q, uint32_t px, uint32_t py, uint32_t s, float r,
-                                                    float g, float b)
-{
-    const uint32_t rx = px - Q.rec_x0, ry = py - Q.rec_y0;
-    if (rx >= Q.rec_w || ry >= Q.rec_h) return;
-    volatile uint32_t *o = reinterpret_cast<volatile uint32_t *>(Q.recs + (size_t(ry) * Q.rec_w + rx) * Q.spp + s);
-    o[8] = __float_as_uint(r);
-    o[9] = __float_as_uint(g);
-    o[10] = __float_as_uint(b);
-}
-
-// One per-sample record (rt_sample_rec) of a product kernel, for samples inside the requested
-// rectangle: rec[((y - y0) * w + (x - x0)) * spp + s], in RAW form -- what the walk leaves, with no
-// extra lookups in the product kernels (their register budget decides their occupancy): a hit's CSR
-// reference (tri word), a miss's end cell as the walk holds it (voxel word, still inside its copy of
-// the cell words).  k_record_fixup then maps the reference to Grid::Intersect's tri_idx and the cell
-// it lies in, and moves a raw end cell out of its copy (kRecRaw* in the pad word).  DDA steps and
-// tests are not counted by the product walks (0xFFFFFFFF; k_trace_records pins them).
-constexpr uint32_t kRecMagic = 0xF1A90000u;     // pad word of a raw record (a -1-filled word is not)
-constexpr uint32_t kRecRawCsr = 1u;             // tri word = CSR reference of the hit
-constexpr uint32_t kRecRawBox = 2u;             // voxel word = end cell in the ray's box-word copy
-constexpr uint32_t kRecRawOct = 4u;             // voxel word = end cell in the ray's octant copy
-__device__ __forceinline__ void store_record(const KParams& Q, uint32_t px, uint32_t py, uint32_t s, bool hit,
-                                             uint32_t tri, uint32_t voxel, float t, float u, float v, uint32_t raw)
-{
-    const uint32_t rx = px - Q.rec_x0, ry = py - Q.rec_y0;
-    if (rx >= Q.rec_w || ry >= Q.rec_h) return;
-    // word by word (volatile: no dwordx4 merging, which needs consecutive VGPRs)
-    volatile uint32_t *o = reinterpret_cast<volatile uint32_t *>(Q.recs + (size_t(ry) * Q.rec_w + rx) * Q.spp + s);
-    o[0] = hit ? 1u : 0u;
-    o[1] = hit ? tri : rtd::kNoTri;
-    o[2] = hit ? rtd::kNoTri : voxel;
-    o[3] = 0xFFFFFFFFu;
-    o[4] = 0xFFFFFFFFu;
-    o[5] = hit ? __float_as_uint(t) : 0u;
-    o[6] = hit ? __float_as_uint(u) : 0u;
-    o[7] = hit ? __float_as_uint(v) : 0u;
-    o[11] = kRecMagic | (hit ? (raw & kRecRawCsr) : (raw & ~kRecRawCsr));
 }
 
 // grid.cpp:159-281 Grid::Intersect (NEW_GRID_TRAVERSAL), axis arrays unrolled into scalars
@@ -1215,531 +1044,6 @@ __device__ __forceinline__ bool grid_intersect(const KParams& P, float ox, float
     }
     if constexpr (!STATS) voxel = uint32_t(cell - (rem0 < 0 ? cs0 : (rem1 < 0 ? cs1 : cs2)));   // records only
     return false;
-}
-
-// Renderer::IntersectBruteForce (renderer.cpp:157-197): every triangle in index order, the
-// closest accepted hit wins, ties keep the lower index (strict '<', :187).  All lanes of a wave
-// walk the same triangle sequence, so the records arrive through wave-uniform (scalar) loads
-// and the wave-gated test skips a triangle's second half when no lane can still hit it.
-template <bool STATS>
-__device__ __forceinline__ bool brute_intersect(const KParams& P, float ox, float oy, float oz, float dx, float dy,
-                                                float dz, float& t, float& u, float& v, uint32_t& tri,
-                                                uint32_t& tests)
-{
-    t = rtd::kFltMax;
-    for (uint32_t i = 0; i < P.ntris; i++)
-    {
-        const float4 a = P.tri_mt[3 * i + 0], b = P.tri_mt[3 * i + 1], c = P.tri_mt[3 * i + 2];
-        float ct = 0.0f, cu = 0.0f, cv = 0.0f;
-        const bool h = rtd::ray_tri_mt_gated(ox, oy, oz, dx, dy, dz, a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x,
-                                             ct, cu, cv);
-        if (h && ct < t)
-        {
-            t = ct;
-            u = cu;
-            v = cv;
-            tri = i;
-        }
-    }
-    if (STATS) tests = P.ntris;
-    return t != rtd::kFltMax;
-}
-
-// Renderer::RayMarch (renderer.cpp:24-41) over Renderer::DistanceBruteForce (:138-155):
-// sphere tracing from the camera, at most 128 steps, hit when a step's distance < 0.001.
-//
-// DistanceBruteForce is a minimum, and the minimum of a set does not depend on the order it
-// is taken in ((d < dist) ? d : dist never selects a NaN, ties have equal values), so any
-// triangle whose computed distance is provably above the minimum can be skipped, and any member
-// may seed it, without changing a bit.  The records are Morton-sorted into blocks of kDistBlock
-// triangles with an exact float AABB.  Error model: every computed DistancePointTri is the
-// distance to a point of the triangle (the inside branch's convex combination or a clamped
-// segment point) up to ~10 ulp of (|p| + |v|); float box distances are off by a few ulp of the
-// same scale.  margin = 1e-5 * (|p|_inf + scene_scale) (>= 166 ulp) therefore gives
-//   lb(block) - margin <= every computed distance of the block's triangles.
-// Per step and lane: the minimum is seeded with the computed distance to the lane's previous
-// nearest triangle, blocks are swept outward from that triangle's block (lane 0's), and a block
-// is skipped when lb - margin > running minimum for every active lane (wave-uniform branch).
-//
-// Miss early-out: once p is outside the vertex AABB with box distance Db, receding from it at a
-// rate r = dir . (p - clamp(p)) / Db >= 2e-5, and Db > 1.00001 * (margin + 0.001), every later
-// point p' = p + s * dir has Db' >= Db + r s and margin' <= margin + 1e-5 s (|dir| <= 1), so
-// every later computed distance exceeds 0.001: the reference marches to its 128-step limit
-// without a hit (renderer.cpp:30-40).  The march stops there and reports exactly that.
-__device__ __forceinline__ void march_eval_block(const KParams& P, uint32_t b, float px, float py, float pz,
-                                                 float& dist, uint32_t& best_k)
-{
-    const uint32_t k0 = b * kDistBlock, k1 = min(k0 + kDistBlock, P.ntris);
-    for (uint32_t k = k0; k < k1; k++)
-    {
-        const float4 *r = P.tri_dist + 6 * size_t(k);
-        const float d = rtd::dist_point_tri(px, py, pz, r[0], r[1], r[2], r[3], r[4], r[5]);
-        if (d < dist)
-        {
-            dist = d;
-            best_k = k;
-        }
-    }
-}
-
-// true when block b can still lower some active lane's minimum
-__device__ __forceinline__ bool march_block_needed(const KParams& P, uint32_t b, float px, float py, float pz,
-                                                   float margin, float dist)
-{
-    const float4 mn = P.dist_blk[2 * b], mx = P.dist_blk[2 * b + 1];
-    const float ex = fmaxf(fmaxf(mn.x - px, px - mx.x), 0.0f);
-    const float ey = fmaxf(fmaxf(mn.y - py, py - mx.y), 0.0f);
-    const float ez = fmaxf(fmaxf(mn.z - pz, pz - mx.z), 0.0f);
-    const float lb = __builtin_sqrtf(ex * ex + ey * ey + ez * ez) - margin;
-    return __any(!(lb > dist));
-}
-
-template <bool STATS, bool EXHAUSTIVE>
-__device__ __forceinline__ bool ray_march(const KParams& P, float ox, float oy, float oz, float dx, float dy,
-                                          float dz, float& t, uint32_t& steps, uint32_t& tests)
-{
-    t = 0.0f;
-    uint32_t best_k = 0;                 // sorted index of the previous step's nearest triangle
-    for (uint32_t s = 0; s < kMarchSteps; s++)
-    {
-        const float px = ox + t * dx, py = oy + t * dy, pz = oz + t * dz;
-        float dist = rtd::kFltMax;
-        if (EXHAUSTIVE)
-        {
-            for (uint32_t i = 0; i < P.ntris; i++)
-            {
-                const float4 *r = P.tri_dist + 6 * size_t(i);
-                const float d = rtd::dist_point_tri(px, py, pz, r[0], r[1], r[2], r[3], r[4], r[5]);
-                dist = (d < dist) ? d : dist;                        // std::min(dist, d)
-            }
-            if (STATS) tests += P.ntris;
-        }
-        else
-        {
-            const float margin = 1e-5f * (fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz)) + P.scene_scale);
-            {
-                const float wx = px - fminf(fmaxf(px, P.smin[0]), P.smax[0]);
-                const float wy = py - fminf(fmaxf(py, P.smin[1]), P.smax[1]);
-                const float wz = pz - fminf(fmaxf(pz, P.smin[2]), P.smax[2]);
-                const float db = __builtin_sqrtf(wx * wx + wy * wy + wz * wz);
-                const float rate = dx * wx + dy * wy + dz * wz;
-                if (db > 1.00001f * (margin + 0.001f) && rate >= 2e-5f * db)
-                {
-                    if (STATS) steps = kMarchSteps;
-                    return false;
-                }
-            }
-            {
-                // the seed enters as any other member does: (d < dist) never selects a NaN (a triangle with
-                // coinciding vertices), which as a plain assignment would keep every later d < dist false
-                const float4 *r = P.tri_dist + 6 * size_t(best_k);
-                const float d = rtd::dist_point_tri(px, py, pz, r[0], r[1], r[2], r[3], r[4], r[5]);
-                dist = (d < dist) ? d : dist;
-            }
-            uint32_t evals = 1;
-            const uint32_t start = __builtin_amdgcn_readfirstlane(best_k / kDistBlock);
-            for (uint32_t b = start; b < P.ndist_blk; b++)
-            {
-                if (!march_block_needed(P, b, px, py, pz, margin, dist)) continue;
-                march_eval_block(P, b, px, py, pz, dist, best_k);
-                evals += min(b * kDistBlock + kDistBlock, P.ntris) - b * kDistBlock;
-            }
-            for (uint32_t b = start; b-- > 0;)
-            {
-                if (!march_block_needed(P, b, px, py, pz, margin, dist)) continue;
-                march_eval_block(P, b, px, py, pz, dist, best_k);
-                evals += min(b * kDistBlock + kDistBlock, P.ntris) - b * kDistBlock;
-            }
-            if (STATS) tests += evals;
-        }
-        t += dist;
-        if (STATS) steps = s + 1;
-        if (dist < 0.001f) return true;
-    }
-    return false;
-}
-
-// What a product walk leaves for rt_render_records_device: hit, t, u, v, the CSR reference of the hit
-// and the walk's end cell (raw: a box-run miss's cell still in its box-word copy).
-struct SampleOut { bool hit; float t, u, v; uint32_t voxel, csr; };
-
-// renderer.cpp:121: the colour of a sample that hits nothing (trace_sample; row_miss_word)
-__device__ __forceinline__ float miss_colour(uint32_t py, uint32_t H) { return float(py) / float(H); }
-
-// renderer.cpp:88-122: one sample -> its colour contribution; hit_tri = the hit triangle
-// (Grid::Intersect's tri_idx, renderer.cpp:105) or kNoTri
-// (trace_sample_at: from the sample's camera-space x, y -- KParams::ndcx / ndcy entries the caller has loaded)
-template <bool STATS, int TRI, int VAR>
-__device__ __forceinline__ void trace_sample_at(const KParams& P, float cam_x, float cam_y, uint32_t py, float& cr,
-                                                float& cg, float& cb, uint32_t& hit_tri, rt_sample_rec *rec,
-                                                uint32_t off = 0u, SampleOut *so = nullptr)
-{
-    float dx, dy, dz;
-    rtd::dir_from_xy(P.m, cam_x, cam_y, dx, dy, dz);                                       // camera.h:8-47
-    float t = 0.0f, u = 0.0f, v = 0.0f;
-    uint32_t tri = rtd::kNoTri, voxel = rtd::kNoTri, steps = 0, tests = 0;
-    bool hit;
-    if constexpr ((VAR & kVarMarch) != 0)
-        hit = ray_march<STATS, (VAR & kVarExhaustive) != 0>(P, P.org[0], P.org[1], P.org[2], dx, dy, dz, t, steps,
-                                                             tests);
-    else if constexpr ((VAR & kVarBrute) != 0)
-        hit = brute_intersect<STATS>(P, P.org[0], P.org[1], P.org[2], dx, dy, dz, t, u, v, tri, tests);
-    else
-        hit = grid_intersect<STATS, TRI, VAR>(P, P.org[0], P.org[1], P.org[2], dx, dy, dz, t, u, v, tri, voxel,
-                                              steps, tests);
-    const KParams& Q = late_params(P, off);
-    constexpr bool CSR_TRI = (VAR & (kVarMarch | kVarBrute)) == 0 && (VAR & kVarOriginPre) && TRI == RT_TRI_MOLLER_TRUMBORE;
-    if (so)                     // the walk's outcome for a record (process_item stores it)
-    {
-        so->hit = hit;
-        so->t = t;
-        so->u = u;
-        so->v = v;
-        so->voxel = voxel;
-        so->csr = CSR_TRI ? tri : rtd::kNoTri;
-    }
-    if constexpr (CSR_TRI)
-        if (hit) tri = __float_as_uint(Q.refs[3 * size_t(tri) + 2].y);     // CSR reference -> triangle id
-    if constexpr ((VAR & kVarMarch) != 0)
-    {
-        // The reference's RayMarch leaves u, v, tri_idx unset (renderer.cpp:103), so the
-        // march is shaded by depth: the reference's own alternative at renderer.cpp:118.
-        if (hit) cr = cg = cb = t / 3.0f;
-        else cr = cg = cb = float(py) / float(Q.H);
-    }
-    else if (hit)
-    {
-        const float4 a = Q.shade[3 * tri + 0], b = Q.shade[3 * tri + 1], c = Q.shade[3 * tri + 2];
-        rtd::shade_hit(u, v, a, b, c, cr, cg, cb);
-    }
-    else
-    {
-        cr = cg = cb = miss_colour(py, Q.H);                     // renderer.cpp:121
-    }
-    hit_tri = hit ? tri : rtd::kNoTri;
-    if (STATS)
-    {
-        rec->hit = hit;
-        rec->tri = hit ? tri : rtd::kNoTri;
-        rec->voxel = voxel;
-        rec->steps = steps;
-        rec->tests = tests;
-        rec->t = hit ? t : 0.0f;
-        rec->u = hit ? u : 0.0f;
-        rec->v = hit ? v : 0.0f;
-        rec->r = cr; rec->g = cg; rec->b = cb;
-        rec->pad = 0;
-    }
-}
-
-template <bool STATS, int TRI, int VAR>
-__device__ __forceinline__ void trace_sample(const KParams& P, uint32_t px, uint32_t py, uint32_t s, float& cr,
-                                             float& cg, float& cb, uint32_t& hit_tri, rt_sample_rec *rec,
-                                             uint32_t off = 0u, SampleOut *so = nullptr)
-{
-    trace_sample_at<STATS, TRI, VAR>(P, P.ndcx[px * P.spp + s], P.ndcy[py * P.spp + s], py, cr, cg, cb, hit_tri, rec,
-                                     off, so);
-}
-
-// Tile bookkeeping: block -> (local tile k, sub-block)
-struct TileCoord { uint32_t k, sub, tx0, ty0; };
-
-__device__ __forceinline__ TileCoord tile_of_block(const KParams& P)
-{
-    TileCoord c;
-    c.k = blockIdx.x / P.wg_per_tile;
-    c.sub = blockIdx.x - c.k * P.wg_per_tile;
-    uint32_t tx, ty;
-    shard_tile_xy(c.k, P.rank, P.nranks, P.tiles_x, tx, ty);
-    c.tx0 = P.rx0 + tx * kTile;
-    c.ty0 = P.ry0 + ty * kTile;
-    return c;
-}
-
-__device__ __forceinline__ void store_pixel(const KParams& P, const TileCoord& c, uint32_t p, uint32_t x,
-                                            uint32_t y, uint32_t word)
-{
-    if (P.shard_mode == 2u)
-    {
-        // the Framebuffer's tile buffers back to back in tile order c + r * fb_tx: tile (c, r) starts
-        // at y0 * W + th_r * x0 (the tiles above it, then the row's tiles left of it, all th_r tall),
-        // pixel (x, y) at buf[(x - x0) + (y - y0) * tw_c] (renderer.cpp:133).  x, y < 2^16 and the
-        // tile sizes < 2^16, so the mul_hi quotients are exact.
-        const uint32_t c = P.fb_tw ? min(__umulhi(x, P.fb_mtw), P.fb_tx - 1u) : P.fb_tx - 1u;
-        const uint32_t r = P.fb_th ? min(__umulhi(y, P.fb_mth), P.fb_ty - 1u) : P.fb_ty - 1u;
-        const uint32_t x0 = c * P.fb_tw, y0 = r * P.fb_th;
-        const uint32_t tw = c == P.fb_tx - 1u ? P.W - x0 : P.fb_tw;
-        const uint32_t th = r == P.fb_ty - 1u ? P.H - y0 : P.fb_th;
-        P.out[size_t(y0) * P.W + size_t(th) * x0 + (y - y0) * tw + (x - x0)] = word;
-    }
-    else if (P.shard_mode)
-        P.out[size_t(c.k) * kTilePix + compact_bits(p >> 1) * kTile + compact_bits(p)] = word;
-    else
-        P.out[size_t(y - P.ry0) * P.pitch + (x - P.rx0)] = word;     // renderer.cpp:133
-}
-
-// renderer.cpp:124 col / float(spp); exact as a multiply when spp is a power of two
-__device__ __forceinline__ float average(const KParams& P, float sum)
-{
-    return P.inv_spp != 0.0f ? sum * P.inv_spp : sum / float(P.spp);
-}
-
-struct ItemCoord { TileCoord c; uint32_t p, s, x, y; bool valid; };
-
-// Sample slot `slot` (pixel-major, Morton pixel order) of local tile k.
-__device__ __forceinline__ ItemCoord tile_slot_coord(const KParams& P, uint32_t k, uint32_t slot)
-{
-    ItemCoord ic;
-    ic.c.k = k;
-    uint32_t tx, ty;
-    shard_tile_xy(k, P.rank, P.nranks, P.tiles_x, tx, ty);
-    ic.c.tx0 = P.rx0 + tx * kTile;
-    ic.c.ty0 = P.ry0 + ty * kTile;
-    ic.p = slot >> P.spp_shift;                               // pixel index in the tile (Morton)
-    ic.s = slot & (P.spp - 1u);
-    ic.x = ic.c.tx0 + compact_bits(ic.p);
-    ic.y = ic.c.ty0 + compact_bits(ic.p >> 1);
-    ic.valid = ic.x < P.rx0 + P.rw && ic.y < P.ry0 + P.rh;
-    return ic;
-}
-
-// Pixel/sample of this lane in work item `item` (wave-uniform): the compact kernel's and the wide
-// section's form, for any tile size (process_item has its own, item_coord_pre / item_coord_post).
-__device__ __forceinline__ ItemCoord item_coord(const KParams& P, uint32_t item, uint32_t lane)
-{
-    const uint32_t items_per_tile = P.wg_per_tile * kWavesPerWG;
-    const uint32_t kseq = item / items_per_tile;              // position in the launch's tile order
-    const uint32_t slot = (item - kseq * items_per_tile) * 64u + lane;
-    return tile_slot_coord(P, P.tile_order ? P.tile_order[kseq] : kseq, slot);   // local tile k
-}
-
-// process_item's form of item_coord.  Before the walk (item_coord_pre): the same coordinates with the
-// two u32 divisions replaced -- the work items per tile are a power of two in every lane kernel
-// (P.ipt_shift), and the shard deal divides by P.tiles_x through its magic (shard_tile_xy_m).  The
-// item's TILE ORIGIN then crosses the walk in ONE packed VGPR (tile_origin_word: tx0 | ty0 << 16 --
-// every launched tile holds a pixel of the region, so tx0 < rx0 + rw <= 65536 and ty0 likewise:
-// validate_frame; wave-uniform, but kept in a VGPR: the kernel has no SGPR to spare across the walk),
-// and item_coord_post rebuilds the whole ItemCoord from it in full 32-bit arithmetic, so a lane of a
-// tile that overhangs the region (x or y up to 15 past it, past 2^16 too) is invalid exactly as
-// item_coord finds it: the Morton offsets come from the lane, the sample is the lane's low bits,
-// validity the same two compares.
-// (slot_coord_m: sample slot `slot` of local tile k, tile_slot_coord with the shard deal's magic division; k_miss_mask
-// takes the corner lanes of an item in the launch's natural order from it)
-__device__ __forceinline__ ItemCoord slot_coord_m(const KParams& P, uint32_t k, uint32_t slot)
-{
-    ItemCoord ic;
-    ic.c.k = k;
-    uint32_t tx, ty;
-    shard_tile_xy_m(ic.c.k, P.rank, P.nranks, P.tiles_x, P.tiles_x_m, tx, ty);
-    ic.c.tx0 = P.rx0 + tx * kTile;
-    ic.c.ty0 = P.ry0 + ty * kTile;
-    ic.p = slot >> P.spp_shift;
-    ic.s = slot & (P.spp - 1u);
-    ic.x = ic.c.tx0 + compact_bits(ic.p);
-    ic.y = ic.c.ty0 + compact_bits(ic.p >> 1);
-    ic.valid = ic.x < P.rx0 + P.rw && ic.y < P.ry0 + P.rh;
-    return ic;
-}
-
-__device__ __forceinline__ ItemCoord item_coord_pre(const KParams& P, uint32_t item, uint32_t lane)
-{
-    const uint32_t kseq = item >> P.ipt_shift;                // position in the launch's tile order
-    const uint32_t slot = ((item - (kseq << P.ipt_shift)) << 6) + lane;
-    return slot_coord_m(P, P.tile_order ? P.tile_order[kseq] : kseq, slot);    // local tile k
-}
-
-// The miss skip: bit `local tile k * items per tile + item in tile` of KParams::miss_mask -- the
-// launch's NATURAL item order, whatever tile_order says -- is set when k_miss_mask proved that every sample of
-// the item misses the grid box (rt_miss_mask.h).  Wave-uniform: one scalar load (process_item issues it beside the
-// item's other prologue words) and a bit test.
-__device__ __forceinline__ uint32_t item_flag_index(const KParams& P, uint32_t item, uint32_t k)
-{
-    return (k << P.ipt_shift) + (item & ((1u << P.ipt_shift) - 1u));
-}
-
-// A wave-uniform word read through the scalar cache (words a kernel wrote and finished before this
-// one was dispatched -- the plan's marks, the miss mask -- as the per-origin records of test_cell are read).
-__device__ __forceinline__ uint32_t uniform_word(const uint32_t *p)
-{
-    return *(const __attribute__((address_space(4))) uint32_t *)(uint64_t(p));
-}
-// ... and a word that can always be read, for the loads of a group that have nothing to fetch: the kernel's arguments
-__device__ __forceinline__ const uint32_t *spare_word()
-{
-    return (const uint32_t *)uint64_t(__builtin_amdgcn_kernarg_segment_ptr());
-}
-
-// The resolve of one pixel (renderer.cpp:124-133), shared by process_item and k_miss_mask's row table.
-// resolve_channel4: one channel of the spp-4 quad form, from the sum of its four samples (c * 0.25f is exact);
-// resolve_word: the generic form, from the three sums.
-__device__ __forceinline__ uint32_t resolve_channel4(float c) { return rtd::pack_channel(rtd::gamma_half(c * 0.25f)); }
-__device__ __forceinline__ uint32_t resolve_word(const KParams& Q, float sr, float sg, float sb)
-{
-    return rtd::pack_bgra8(rtd::gamma_half(average(Q, sr)), rtd::gamma_half(average(Q, sg)), rtd::gamma_half(average(Q, sb)));
-}
-
-// The packed BGRA word of a pixel of row y whose samples all miss (KParams::rowmiss[y]): process_item's own
-// sums and resolve on spp copies of the miss colour -- the quad form at spp 4 (the sum starts at the first
-// sample), the generic form otherwise (the sum starts at 0.0f).
-__device__ __forceinline__ uint32_t row_miss_word(const KParams& P, uint32_t y)
-{
-    const float c = miss_colour(y, P.H);
-    if (P.spp == 4u)
-    {
-        const uint32_t v = resolve_channel4(c + c + c + c);
-        return v | (v << 8) | (v << 16);
-    }
-    float sum = 0.0f;
-    for (uint32_t k = 0; k < P.spp; k++) sum += c;
-    return resolve_word(P, sum, sum, sum);
-}
-
-// The tile origin of an ItemCoord as one word held in a VGPR (the empty asm keeps the compiler from
-// carrying the wave-uniform value in an SGPR across the walk).
-__device__ __forceinline__ uint32_t tile_origin_word(const ItemCoord& ic)
-{
-    uint32_t w = ic.c.tx0 | (ic.c.ty0 << 16);
-    asm volatile("" : "+v"(w));
-    return w;
-}
-
-__device__ __forceinline__ ItemCoord item_coord_post(const KParams& Q, uint32_t item, uint32_t lane, uint32_t origin)
-{
-    const uint32_t kseq = item >> Q.ipt_shift;
-    const uint32_t o = __builtin_amdgcn_readfirstlane(origin);
-    ItemCoord ic;
-    ic.c.k = Q.tile_order ? Q.tile_order[kseq] : kseq;
-    ic.c.tx0 = o & 0xFFFFu;
-    ic.c.ty0 = o >> 16;
-    ic.p = (((item - (kseq << Q.ipt_shift)) << 6) + lane) >> Q.spp_shift;
-    ic.s = lane & (Q.spp - 1u);
-    ic.x = ic.c.tx0 + compact_bits(ic.p);
-    ic.y = ic.c.ty0 + compact_bits(ic.p >> 1);
-    ic.valid = ic.x < Q.rx0 + Q.rw && ic.y < Q.ry0 + Q.rh;
-    return ic;
-}
-
-// The record of one sample of AUTO's walk (rt_render_records_device), raw (store_record): a box-run
-// miss's end cell is still in its box-word copy.
-template <int VAR>
-__device__ __forceinline__ void process_record(const KParams& Q, const ItemCoord& ic, const SampleOut& so, float cr,
-                                               float cg, float cb)
-{
-    constexpr uint32_t box = ((VAR & kVarSkipRun) && (VAR & kVarPackedRem)) ? kRecRawBox : 0u;
-    store_record(Q, ic.x, ic.y, ic.s, so.hit, so.csr, so.voxel, so.t, so.u, so.v,
-                 (so.csr != rtd::kNoTri ? kRecRawCsr : 0u) | (so.voxel < kVoxelUnknown ? box : 0u));
-    store_record_colour(Q, ic.x, ic.y, ic.s, cr, cg, cb);
-}
-
-// One wave-sized work item = 64 consecutive sample slots of a 16x16 tile in Morton order
-// (a 2^k x 2^k pixel block x spp samples).  Traces the lane's sample, sums the pixel's
-// samples across its adjacent lanes in sample order (renderer.cpp:87-122, hazard H10) and
-// stores the packed pixel (renderer.cpp:124-133).
-//
-// The item's head (item_head) is everything its prologue reads from memory, sent out as ONE group:
-// the plan mark of the item's block (block_of_launch; the caller tests it) and the miss-mask word -- wave-uniform:
-// scalar loads -- and the lane's two camera-space table entries.  None of the four addresses depends on another's
-// value, so all are issued before the first test that reads one and waited for once.  A load with nothing to fetch
-// reads a spare word (no mark, no mask) or entry 0 of its table (a lane outside the region), so every address is in
-// bounds for every launched block; the tests then read what has arrived, in the order they always had.
-struct ItemHead { ItemCoord ic; uint32_t mark_w, mask_w, flag; float cam_x, cam_y; };
-
-// the miss skip (AUTO's lane kernels on the grid walk; the host passes a mask only to frames without hit
-// IDs or records): a flagged item's pixels take the row's all-miss word, and no ray is generated
-template <int TRI, int VAR>
-constexpr bool kItemMissSkip = TRI == RT_TRI_MOLLER_TRUMBORE && (VAR & kVarAutoCore) == kVarAutoCore &&
-                               (VAR & (kVarWaveClock | kVarLdsSplit | kVarMarch | kVarBrute | kVarRays)) == 0;
-
-// item: wave-uniform (readfirstlane'd by the caller); mark: the block's plan mark, or null
-template <int TRI, int VAR>
-__device__ __forceinline__ ItemHead item_head(const KParams& P, uint32_t item, const uint32_t *mark = nullptr)
-{
-    ItemHead h;
-    h.ic = item_coord_pre(P, item, threadIdx.x & 63u);
-    const ItemCoord& ic = h.ic;
-    h.flag = kItemMissSkip<TRI, VAR> ? item_flag_index(P, item, ic.c.k) : 0u;
-    h.mark_w = uniform_word(mark ? mark : spare_word());
-    h.mask_w = kItemMissSkip<TRI, VAR> ? uniform_word(P.miss_mask ? P.miss_mask + (h.flag >> 5) : spare_word()) : 0u;
-    h.cam_x = P.ndcx[ic.valid ? ic.x * P.spp + ic.s : 0u];
-    h.cam_y = P.ndcy[ic.valid ? ic.y * P.spp + ic.s : 0u];
-    asm volatile("" : "+s"(h.mark_w), "+s"(h.mask_w), "+v"(h.cam_x), "+v"(h.cam_y));     // the group's one wait
-    return h;
-}
-
-template <int TRI, int VAR>
-__device__ __forceinline__ void process_item(const KParams& P, uint32_t item, uint32_t off, const ItemHead& h)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    float cr = 0.0f, cg = 0.0f, cb = 0.0f;
-    uint32_t hit_tri = rtd::kNoTri;
-    SampleOut so{false, 0.0f, 0.0f, 0.0f, rtd::kNoTri, rtd::kNoTri};
-    uint32_t origin;
-    {
-        const ItemCoord& ic = h.ic;
-        if constexpr (kItemMissSkip<TRI, VAR>)
-            if (P.miss_mask && ((h.mask_w >> (h.flag & 31u)) & 1u) != 0u)
-            {
-                if (ic.valid && ic.s == 0) store_pixel(P, ic.c, ic.p, ic.x, ic.y, P.rowmiss[ic.y]);
-                return;
-            }
-        origin = tile_origin_word(ic);
-        if (ic.valid)
-            trace_sample_at<false, TRI, VAR>(P, h.cam_x, h.cam_y, ic.y, cr, cg, cb, hit_tri, nullptr, off, &so);
-    }
-    const KParams& Q = late_params(P, off);
-    const ItemCoord ic = item_coord_post(Q, item, lane, origin);
-    // kVarLdsSplit: the workgroup's four waves traced the same samples; wave 0 stores them
-    const bool owner = (VAR & kVarLdsSplit) == 0 || threadIdx.x < 64u;
-    // rt_render_hits_device only: the sample's hit triangle, after the walk (a scalar test of a
-    // kernel parameter; the walk above is the same code whatever the pointer holds)
-    if (Q.hits && ic.valid && owner) Q.hits[(size_t(ic.y) * Q.W + ic.x) * Q.spp + ic.s] = hit_tri;
-    // rt_render_records_device only, likewise: the sample's record (process_record)
-    if (Q.recs && ic.valid && owner) process_record<VAR>(Q, ic, so, cr, cg, cb);
-    float sr = 0.0f, sg = 0.0f, sb = 0.0f;
-    if (Q.spp == 4u)
-    {
-        // the bench's 4 spp: a pixel's samples are one quad of lanes, so each sample's colour is
-        // a quad broadcast (DPP, one VALU) instead of an LDS permute; same values, same order.
-        // renderer.cpp:87-122 starts the sum at 0.0f; 0.0f + x == x for every colour (>= +0:
-        // (n + 1) * 0.5 of a normalised component, py / H, t / 3 -- never -0), so the sum
-        // starts at the first sample
-        sr = quad_bcast<0>(cr) + quad_bcast<1>(cr) + quad_bcast<2>(cr) + quad_bcast<3>(cr);
-        sg = quad_bcast<0>(cg) + quad_bcast<1>(cg) + quad_bcast<2>(cg) + quad_bcast<3>(cg);
-        sb = quad_bcast<0>(cb) + quad_bcast<1>(cb) + quad_bcast<2>(cb) + quad_bcast<3>(cb);
-        // ... and the quad's lanes 0, 1, 2 resolve one channel each (b, g, r: the byte at their
-        // position in pack_bgra8's word; lane 3 contributes the zero alpha byte), so the correctly
-        // rounded square root and the packing run once per wave instead of three times; the
-        // bytes meet in the pixel's lane by quad broadcasts (same per-channel arithmetic)
-        const uint32_t j = lane & 3u;
-        const float c = j == 0u ? sb : (j == 1u ? sg : sr);
-        uint32_t v = resolve_channel4(c) << (8u * j);            // renderer.cpp:124, exact
-        v = j == 3u ? 0u : v;
-        const uint32_t word = quad_bcast_u<0>(v) | quad_bcast_u<1>(v) | quad_bcast_u<2>(v);
-        if (ic.valid && ic.s == 0 && owner) store_pixel(Q, ic.c, ic.p, ic.x, ic.y, word);
-        return;
-    }
-    else
-    {
-        const uint32_t base = lane & ~(Q.spp - 1u);
-        for (uint32_t k = 0; k < Q.spp; k++)
-        {
-            sr += __shfl(cr, int(base + k), 64);
-            sg += __shfl(cg, int(base + k), 64);
-            sb += __shfl(cb, int(base + k), 64);
-        }
-    }
-    if (ic.valid && ic.s == 0 && owner)
-    {
-        store_pixel(Q, ic.c, ic.p, ic.x, ic.y, resolve_word(Q, sr, sg, sb));
-    }
-}
-
-// an item with no plan mark to test (the wide section's LDS tier)
-template <int TRI, int VAR>
-__device__ __forceinline__ void process_item(const KParams& P, uint32_t item, uint32_t off = 0u)
-{
-    item = __builtin_amdgcn_readfirstlane(item);
-    process_item<TRI, VAR>(P, item, off, item_head<TRI, VAR>(P, item));
 }
 
 } // namespace

@@ -11,9 +11,18 @@ import subprocess
 import pytest
 
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-# csrc/Makefile's FLAGS, for the device side alone
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
-         "--cuda-device-only"]
+_CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                     "cpp-11-ray-trace-march-framework_amd", "csrc")
+
+
+def makefile_words(target):
+    """What csrc/Makefile's print-* target says (print-flags, print-objs, print-hashed), as a list of words."""
+    return subprocess.run(["make", "-s", "--no-print-directory", "-C", _CSRC, target], check=True,
+                          capture_output=True, text=True).stdout.split()
+
+
+# csrc/Makefile's FLAGS, for the device side alone (no -fPIC; the warnings are the build's business)
+FLAGS = [f for f in makefile_words("print-flags") if f not in ("-fPIC", "-Wall")] + ["--cuda-device-only"]
 needs_hipcc = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 
 _FIELDS = (r"TotalSGPRs: (\d+)", r" VGPRs: (\d+)", r"ScratchSize \[bytes/lane\]: (\d+)",

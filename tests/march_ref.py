@@ -97,7 +97,7 @@ def stop_condition(o, d, pos, vmin, vmax, scale, min_dist):
 
 
 def frame_stop_condition(d, pos, vmin, vmax, scale):
-    """The receding-miss stop of the FRAME march (ray_march's culled arm, csrc/rt_walk.h) at a step's position, its
+    """The receding-miss stop of the FRAME march (ray_march's culled arm, csrc/rt_frame_isect.h) at a step's position, its
     float operations in their order -> bool [n].  Unlike the query's (stop_condition) it has neither the |dir|_1 factor
     nor the E term: min_dist is 0.001, the rate threshold 2e-5 db whatever the direction's length.
 

@@ -6,7 +6,7 @@
    camera_matrices.generate_rays against every march window, bit for bit; the rays of a window are split over the
    restatement's thread pool (serially the worst case, an all-miss window of scene 8, takes about 36 s; stack1500's
    windows 1 to 4 s).
-3. The frame march's receding-miss stop (march_ref.frame_stop_condition: ray_march's operations in csrc/rt_walk.h):
+3. The frame march's receding-miss stop (march_ref.frame_stop_condition: ray_march's operations in csrc/rt_frame_isect.h):
    every ray it ends anywhere is a miss of the whole 128-step loop -- for directions of length 2^0 ... 2^20, floors
    of half-extent 1 ... 4,096 under nearly parallel rays, and the far eyes of the fixture.
 """

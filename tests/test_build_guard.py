@@ -17,6 +17,8 @@ from hip_remarks import FLAGS, HIPCC, resource_table
 
 SRC = os.path.join(PKG_DIR, "csrc", "rt_kernels.hip")
 WALK = os.path.join(PKG_DIR, "csrc", "rt_walk.h")
+LAYERS = tuple(os.path.join(PKG_DIR, "csrc", n) for n in ("rt_wave.h", "rt_frame_isect.h", "rt_item_coord.h",
+                                                           "rt_item.h"))
 GRID_SRC = os.path.join(PKG_DIR, "csrc", "rt_grid_build.hip")
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 
@@ -35,11 +37,12 @@ def test_device_ir_has_no_contraction_or_fast_math(tmp_path, src):
     # pixel's arithmetic; tests/test_lane_runs.py); any other llvm.fma would be a contraction in
     # disguise
     assert not re.search(r"\bllvm\.fma\.f64\b", ir)
-    for f in (SRC, WALK, GRID_SRC, os.path.join(PKG_DIR, "csrc", "rt_device.h")):
+    # (every device header of the render kernels: rt_walk.h holds box_exit_bound, the layers split from it hold none)
+    for f in (SRC, WALK, GRID_SRC, os.path.join(PKG_DIR, "csrc", "rt_device.h")) + LAYERS:
         text = open(f).read().splitlines()
         lines = [l for l in text if re.search(r"\bfmaf?\b|__builtin_fma", l)]
         assert all("__builtin_fmaf(" in l for l in lines), lines
-        assert len(lines) == (0 if f in (SRC, GRID_SRC) else 2), (f, lines)
+        assert len(lines) == (0 if f in (SRC, GRID_SRC) + LAYERS else 2), (f, lines)
         if f == WALK:
             i = next(j for j, l in enumerate(text) if "float box_exit_bound(" in l)
             assert all(l in text[i:i + 5] for l in lines), lines

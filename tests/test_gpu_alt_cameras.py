@@ -1,4 +1,4 @@
-"""RT_ISECT_BRUTE_FORCE and RT_ISECT_RAY_MARCH (brute_intersect and ray_march of csrc/rt_walk.h) under cameras whose
+"""RT_ISECT_BRUTE_FORCE and RT_ISECT_RAY_MARCH (brute_intersect and ray_march of csrc/rt_frame_isect.h) under cameras whose
 3x3 is not orthonormal, from eyes on and around the mesh and on meshes with NaN-distance triangles
 (tests/alt_cameras.py): everything the grid walk is pinned on, for the two other per-sample intersectors.
 
