@@ -129,14 +129,10 @@ __device__ __forceinline__ void wide_trace(const KParams& P, uint32_t k, uint32_
                     {
                         const uint32_t b0 = uint32_t(boxw);
                         const int f0 = boxw & 1023, f1 = (boxw >> 11) & 1023, f2 = int(uint32_t(boxw) >> 22);
-                        const float tl = __builtin_fminf(__builtin_fminf(box_exit_bound(nct0, dt0, f0),
-                                                                         box_exit_bound(nct1, dt1, f1)),
-                                                         box_exit_bound(nct2, dt2, f2));
-                        int c0 = 0, c1 = 0, c2 = 0;
-                        while (nct0 < tl && c0 < f0) { nct0 += dt0; c0++; }
-                        while (nct1 < tl && c1 < f1) { nct1 += dt1; c1++; }
-                        while (nct2 < tl && c2 < f2) { nct2 += dt2; c2++; }
-                        boxw -= c0 + (c1 << 11) + (c2 << 22);
+                        // (the guarded chains: rt_lane_run.h says why not the lean ones here)
+                        boxw -= lane_run<false>(nct0, nct1, nct2, dt0, dt1, dt2, box_exit_bound(nct0, dt0, f0),
+                                                box_exit_bound(nct1, dt1, f1), box_exit_bound(nct2, dt2, f2), f0, f1,
+                                                f2);
                         do
                             RT_DDA_BOX_BARE_STEP();
                         while ((uint32_t(boxw) & uint32_t(kRemGuards)) == 0u);

@@ -9,9 +9,16 @@
 
 #include "rt_device.h"
 #include "rt_kparams.h"
+#include "rt_lane_run.h"
 #include "rt_record_gate.h"
 #include "rt_setup_div.h"
 #include "rt_wave.h"
+
+// grid_intersect's per-lane runs take rt_lane_run.h's lean add chains; a unit that defines this false before
+// including the walk keeps the guarded loops alone (rt_ao.hip says why it does)
+#ifndef RT_WALK_LEAN_CHAINS
+#define RT_WALK_LEAN_CHAINS true
+#endif
 
 namespace rtk {
 namespace {
@@ -844,13 +851,11 @@ __device__ __forceinline__ bool grid_intersect(const KParams& P, float ox, float
                 // same cells, crossing times and exits as one step per cell.
                 const uint32_t b0 = uint32_t(boxw);
                 const int f0 = boxw & 1023, f1 = (boxw >> 11) & 1023, f2 = int(uint32_t(boxw) >> 22);
-                const float tl = __builtin_fminf(__builtin_fminf(box_exit_bound(nct0, dt0, f0), box_exit_bound(nct1, dt1, f1)),
-                                                 box_exit_bound(nct2, dt2, f2));
-                int c0 = 0, c1 = 0, c2 = 0;
-                while (nct0 < tl && c0 < f0) { nct0 += dt0; c0++; }
-                while (nct1 < tl && c1 < f1) { nct1 += dt1; c1++; }
-                while (nct2 < tl && c2 < f2) { nct2 += dt2; c2++; }
-                boxw -= c0 + (c1 << 11) + (c2 << 22);
+                // (rt_lane_run.h: tl, the three chains -- wave-uniform trips where the bounds prove the
+                // count guard redundant, else the guarded loops -- and the packed step counts)
+                boxw -= lane_run<RT_WALK_LEAN_CHAINS>(nct0, nct1, nct2, dt0, dt1, dt2, box_exit_bound(nct0, dt0, f0),
+                                                      box_exit_bound(nct1, dt1, f1), box_exit_bound(nct2, dt2, f2), f0,
+                                                      f1, f2);
                 if constexpr (IVAL)
                 {
                     // Rule 3 of the any-hit walk asks after EVERY step whether its crossing was >= tmax; inside
